@@ -18,6 +18,20 @@ time over ranks is used; rank 0 prints ONE JSON line.
 
 Infinity Cache: a 98.3 MB batch fits the 256 MiB MALL, so the bench rotates
 over R distinct copies (default 4 = 393 MB) so every launch reads HBM.
+
+A plain run sets up, issues the W warmup steps, times the K steps and prints
+the line (the headline figures, plus the roofline and timing blocks read off
+the HIP events that bracket those same K steps).  Everything that takes runs
+of its own -- the one-stream reference, the ungated and warm re-times, the
+PCIe-inclusive end-to-end leg, cfg1's host call, the `cfg5_strong` block and
+the CPU baseline -- runs only with --full, where --no-e2e, --no-strong and
+--cpu-seconds 0 still switch single legs off.  `line_problems` describes a
+--full line.
+
+--dump-outputs DIR writes what the last timed step computed (the per-packet
+results a caller of wgcs_checksum_batches receives for that batch) as
+DIR/<name>.npy in float32; the batch is seeded, so two builds run with the
+same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -56,6 +70,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="cfg1/2/3/5: also run what the headline figure does not need: the one-stream reference, the "
+                         "ungated and warm re-times, the end-to-end leg, cfg1's host call, cfg2's cfg5_strong block "
+                         "and the CPU baseline (a plain run times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="cfg1/2/3/5: after the timed steps, write the last timed step's per-packet results as "
+                         "DIR/<name>.npy (float32)")
     ap.add_argument("--config", default="cfg2",
                     choices=sorted(CONFIGS) + ["cfg4", "gro", "gro_staged", "gro_device", "udp_split", "udp_coalesce"])
     ap.add_argument("--mode", default="validate", choices=["validate", "fill"])
@@ -140,6 +161,9 @@ def main():
     args = parse()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs and args.config not in CONFIGS:
+        sys.exit(f"bench.py: --dump-outputs covers the checksum configs ({', '.join(sorted(CONFIGS))}), "
+                 f"not --config {args.config}")
     rc = launch_ranks(args, sys.argv[1:])
     if rc is not None:
         sys.exit(rc)
@@ -226,8 +250,10 @@ def main():
     bytes_per_step = int(pkts_np["len"].astype(np.int64).sum())
     use_events = not args.no_event_timing
     leg = checksum_leg(torch, dev, arena_np, pkts_np, mode, args.steps, args.warmup, args.streams, args.rotate,
-                       barrier, use_events, repeat=args.repeat, verify=args.verify, gate=not args.no_gate,
-                       poll=args.poll, warm_ms=args.warm_ms if scaling == "strong" else 0.0)
+                       barrier, use_events, repeat=args.repeat, verify=args.verify, iso=args.full,
+                       gate=not args.no_gate, poll=args.poll,
+                       warm_ms=args.warm_ms if scaling == "strong" and args.full else 0.0,
+                       dump=bool(args.dump_outputs))
     local_elapsed, kern_ms, iso_ms, S, R = leg["elapsed"], leg["kern_ms"], leg["iso_ms"], leg["streams"], leg["R"]
     elapsed = shard.max_over_ranks(local_elapsed, dist, device=red_dev)
     kern_all = shard.gather_floats(kern_ms if kern_ms is not None else -1.0, dist, device=red_dev)
@@ -300,21 +326,23 @@ def main():
             result["timing"]["repeats"] = [{"wall_us": round(w * 1e6, 1), "event_span_us": round(m * args.steps * 1e3, 1)}
                                            for w, m in leg["repeats"]]
         result["roofline"] = roofline(kname, bytes_per_step, flen, n, kern_ms, S, iso_ms, kern_all)
-    if not args.no_e2e:  # every rank moves its own shard over its own PCIe link; rank 0 reports the aggregate
+    if args.dump_outputs:  # every rank writes its own batch's results
+        dump_outputs(args.dump_outputs, mode, leg["last_out"], n, rank, world)
+    if args.full and not args.no_e2e:  # every rank moves its own shard over its own PCIe link; rank 0 reports the aggregate
         e2e = end_to_end(torch, dev, arena_np, pkts_np, mode, barrier, dist, red_dev, world)
         if rank == 0:
             result["end_to_end"] = e2e
-    if rank == 0 and world == 1 and args.config == "cfg1" and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and args.config == "cfg1" and not args.no_e2e:
         result["host_call"] = host_call(dev, arena_np, pkts_np, mode)
     del leg
     # BASELINE.json configs[4] in the same run: the 1,048,576-frame mixed batch
     # split over the N ranks by bytes (strong scaling), its own roofline
-    if args.config == "cfg2" and not args.no_strong:
+    if args.full and args.config == "cfg2" and not args.no_strong:
         strong = strong_leg(torch, dev, args, mode, rank, world, barrier, dist, red_dev, use_events)
         if rank == 0:
             result["cfg5_strong"] = strong
     # the CPU baseline on rank 0 at every N (north_star: "reported in the same run")
-    if rank == 0 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and args.cpu_seconds > 0:
         result["cpu_baseline"] = cpu_baseline(arena_np, pkts_np, mode, args.cpu_seconds)
     barrier()  # the other ranks wait for rank 0's CPU leg before tearing down
     if rank == 0:
@@ -429,11 +457,15 @@ def gate_streams(dev, bell, streams, use_events) -> list:
 
 
 def checksum_leg(torch, dev, arena_np, pkts_np, mode, steps, warmup, streams, rotate, barrier, use_events,
-                 repeat=1, verify=False, iso=True, gate=True, poll=False, warm_ms=0.0):
+                 repeat=1, verify=False, iso=True, gate=True, poll=False, warm_ms=0.0, dump=False):
     """Time `steps` checksum launches (one batch each, inputs resident in HBM)
     after `warmup` untimed ones.  Returns {elapsed (this rank's wall s),
     kern_ms (HIP events, GPU ms per launch), iso_ms (one-stream reference),
-    repeats, streams, R}."""
+    repeats, streams, R}.  iso=False leaves out the runs the contract region
+    does not need (the one-stream reference and the ungated re-time).
+    dump=True adds last_out: the output buffer of the last timed step, copied
+    right after the region (the buffer is overwritten with 0xA5 before the
+    region, so the copy holds what that step wrote, not a warmup step's)."""
     from wireguard_amd.tun import MODE_VALIDATE
 
     n = len(pkts_np)
@@ -528,7 +560,11 @@ def checksum_leg(torch, dev, arena_np, pkts_np, mode, steps, warmup, streams, ro
             want = (a[np.arange(n), cs].astype(np.uint16) << 8) | a[np.arange(n), cs + 1]
             assert np.array_equal(got, want), "L4_FILL mismatch vs stored checksums"
 
+    last = (warmup + steps - 1) % R  # the rotated copy the last timed step works on
+    if dump:
+        outs[last].fill_(0xA5)
     local_elapsed, kern_ms = timed(steps, warmup, S)
+    last_out = outs[last].cpu().numpy() if dump else None
     repeats = [timed(steps, warmup + r * steps, S) for r in range(1, repeat)]
     # Large launches (configs[4]: 1.57 GB each at N = 1) run ~15 % slower for
     # the first ~25 ms of sustained streaming after the GPU sat idle (the
@@ -557,7 +593,7 @@ def checksum_leg(torch, dev, arena_np, pkts_np, mode, steps, warmup, streams, ro
         _, iso_ms = timed(max(steps, 20), warmup + steps, 1)
     del arenas, outs, pkts
     return {"elapsed": local_elapsed, "kern_ms": kern_ms, "iso_ms": iso_ms, "repeats": repeats, "streams": S, "R": R,
-            "ungated": ungated, "prewarm": prewarm, "warm": warm}
+            "ungated": ungated, "prewarm": prewarm, "warm": warm, "last_out": last_out}
 
 
 def strong_leg(torch, dev, args, mode, rank, world, barrier, dist, red_dev, use_events) -> dict:
@@ -620,6 +656,25 @@ def warm_block(warm_ms, launches, wall, kern_ms, steps) -> dict:
     if kern_ms is not None:
         b["event_span_us"] = round(kern_ms * steps * 1e3, 2)
     return b
+
+
+def dump_outputs(dirname, mode, last_out, n, rank, world) -> str:
+    """--dump-outputs: the per-packet results of the last timed step (one
+    byte per packet for VALIDATE, 1 = checksum valid; the big-endian L4
+    checksum as a 16-bit word for L4_FILL, read as verify does) as float32 in
+    DIR/<name>.npy; N > 1: one file per rank."""
+    from wireguard_amd.tun import MODE_VALIDATE
+
+    if mode == MODE_VALIDATE:
+        name, vals = "checksum_valid", last_out[:n]
+    else:
+        name, vals = "l4_checksum", last_out.view(np.uint16)[:n]
+    if world > 1:
+        name += f"_rank{rank}"
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, name + ".npy")
+    np.save(path, vals.astype(np.float32))
+    return path
 
 
 def _tune_tag():

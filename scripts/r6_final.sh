@@ -29,12 +29,12 @@ step() {  # name limit cmd...
 }
 line() {  # name limit bench-args...
   local name=$1 lim=$2; shift 2
-  step "$name" "$lim" python bench.py "$@"
+  step "$name" "$lim" python bench.py --full "$@"
   grep '^{"metric"' "$OUT/$name.log" | tail -n 1 | sed "s/^{/{\"tag\": \"$name\", /" >> "$OUT/lines.jsonl"
 }
 prof() {  # name bench-args...
   local name=$1; shift
-  (cd /tmp && step "$name" 300 rocprofv3 --kernel-trace --stats -d "$OUT/$name" -o run --output-format csv -- python3 "$ROOT/bench.py" "$@" --cpu-seconds 0 --no-e2e)
+  (cd /tmp && step "$name" 300 rocprofv3 --kernel-trace --stats -d "$OUT/$name" -o run --output-format csv -- python3 "$ROOT/bench.py" --full "$@" --cpu-seconds 0 --no-e2e)
 }
 SIZED="TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_32B_sum"
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES"
@@ -82,7 +82,7 @@ if want prof; then
   prof prof_gro_shuffled_1s --config gro_device --gro-shape shuffled --steps 20 --warmup 2 --streams 1
 fi
 if want sq; then
-  pmcrun sq_cfg2 $SQ -- $ROOT/bench.py --steps 45 --warmup 5 --streams 1 --no-strong --cpu-seconds 0 --no-e2e --no-event-timing
+  pmcrun sq_cfg2 $SQ -- $ROOT/bench.py --full --steps 45 --warmup 5 --streams 1 --no-strong --cpu-seconds 0 --no-e2e --no-event-timing
   pmcrun sq_flat $SQ -- $ROOT/scripts/probe_stream2.py
 fi
 if want pmc; then
@@ -92,12 +92,12 @@ if want pmc; then
 fi
 if want pmccs; then
   for p in "f:FETCH_SIZE" "w:WRITE_SIZE" "s:$SIZED"; do
-    pmcrun pmc${p%%:*}_cfg2 ${p#*:} -- $ROOT/bench.py --steps 30 --warmup 3 --no-strong --cpu-seconds 0 --no-e2e --no-event-timing --streams 1
+    pmcrun pmc${p%%:*}_cfg2 ${p#*:} -- $ROOT/bench.py --full --steps 30 --warmup 3 --no-strong --cpu-seconds 0 --no-e2e --no-event-timing --streams 1
   done
 fi
 if want gloo8; then
   export WGCS_DIST_BACKEND=gloo
-  step gloo8 600 python bench.py --gpus 8 --steps 20 --warmup 5
+  step gloo8 600 python bench.py --full --gpus 8 --steps 20 --warmup 5
   unset WGCS_DIST_BACKEND
   grep '^{"metric"' "$OUT/gloo8.log" | tail -n 1 > "$OUT/rehearse_gpus8_gloo.jsonl"
 fi

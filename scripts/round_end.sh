@@ -23,7 +23,7 @@ step() {  # name limit cmd...
 }
 line() {  # name limit bench-args...
   local name=$1 lim=$2; shift 2
-  step "$name" "$lim" python bench.py "$@"
+  step "$name" "$lim" python bench.py --full "$@"
   grep '^{"metric"' "$OUT/$name.log" | tail -n 1 | sed "s/^{/{\"tag\": \"$name\", /" >> "$OUT/lines.jsonl"
 }
 want() { for a in "${ARGS[@]}"; do [ "$a" = "$1" ] && return 0; done; return 1; }
@@ -54,10 +54,10 @@ if want lines; then
   line udp_coalesce 300 --config udp_coalesce --steps 50 --warmup 5 --cpu-seconds 3
 fi
 if want prof; then
-  (cd /tmp && step prof_driver 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_driver" -o run --output-format csv -- python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --no-e2e --no-strong)
+  (cd /tmp && step prof_driver 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_driver" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --no-e2e --no-strong)
   python3 scripts/trace_span.py "$OUT/prof_driver/run_kernel_trace.csv" checksum_batch 20 20 | sed "s/^{/{\"run\": \"prof_driver\", /" >> "$OUT/trace_span.jsonl"
-  (cd /tmp && step prof_cfg2 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_cfg2" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 200 --warmup 20 --cpu-seconds 0 --no-e2e --no-strong)
-  (cd /tmp && step prof_cfg2_1s 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_cfg2_1s" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 200 --warmup 20 --cpu-seconds 0 --no-e2e --streams 1 --no-strong)
+  (cd /tmp && step prof_cfg2 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_cfg2" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --steps 200 --warmup 20 --cpu-seconds 0 --no-e2e --no-strong)
+  (cd /tmp && step prof_cfg2_1s 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_cfg2_1s" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --steps 200 --warmup 20 --cpu-seconds 0 --no-e2e --streams 1 --no-strong)
   (cd /tmp && step prof_cfg4 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_cfg4" -o run --output-format csv -- python3 "$ROOT/bench.py" --config cfg4 --steps 100 --warmup 10 --cpu-seconds 0 --no-e2e)
   (cd /tmp && step prof_gro_shuffled 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_gro_shuffled" -o run --output-format csv -- python3 "$ROOT/bench.py" --config gro_device --gro-shape shuffled --steps 20 --warmup 2 --cpu-seconds 0 --no-e2e --streams 1)
   (cd /tmp && step prof_cfg4_1s 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_cfg4_1s" -o run --output-format csv -- python3 "$ROOT/bench.py" --config cfg4 --steps 100 --warmup 10 --cpu-seconds 0 --no-e2e --streams 1)
@@ -67,8 +67,8 @@ if want prof; then
   done
 fi
 if want pmc; then
-  (cd /tmp && step pmcf_cfg2 300 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmcf_cfg2" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 30 --warmup 3 --cpu-seconds 0 --no-e2e --no-event-timing --streams 1 --no-strong)
-  (cd /tmp && step pmcw_cfg2 300 timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmcw_cfg2" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 30 --warmup 3 --cpu-seconds 0 --no-e2e --no-event-timing --streams 1 --no-strong)
+  (cd /tmp && step pmcf_cfg2 300 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmcf_cfg2" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --steps 30 --warmup 3 --cpu-seconds 0 --no-e2e --no-event-timing --streams 1 --no-strong)
+  (cd /tmp && step pmcw_cfg2 300 timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmcw_cfg2" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --steps 30 --warmup 3 --cpu-seconds 0 --no-e2e --no-event-timing --streams 1 --no-strong)
   (cd /tmp && step pmcf_cfg4 300 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmcf_cfg4" -o run --output-format csv -- python3 "$ROOT/bench.py" --config cfg4 --steps 30 --warmup 3 --cpu-seconds 0 --no-e2e --no-event-timing --streams 1)
   (cd /tmp && step pmcw_cfg4 300 timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmcw_cfg4" -o run --output-format csv -- python3 "$ROOT/bench.py" --config cfg4 --steps 30 --warmup 3 --cpu-seconds 0 --no-e2e --no-event-timing --streams 1)
   (cd /tmp && step pmcf_gro_shuffled 300 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmcf_gro_shuffled" -o run --output-format csv -- python3 "$ROOT/bench.py" --config gro_device --gro-shape shuffled --steps 10 --warmup 2 --cpu-seconds 0 --no-e2e --streams 1)

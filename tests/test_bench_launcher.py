@@ -3,7 +3,8 @@ runs N ranks under torch.distributed.run as a child process; under a launcher
 WORLD_SIZE must equal --gpus.  CPU tests check the launcher command (run here
 with a stand-in rank script under gloo) and the mismatch exit; the GPU test
 runs the real bench as 2 gloo ranks sharing cuda:0 and reads n_gpus from the
-one JSON line."""
+one JSON line.  The complete line (line_problems) is what `--full` prints; a
+plain run's line and its `--dump-outputs` files have a GPU test of their own."""
 import json
 import os
 import subprocess
@@ -238,7 +239,7 @@ def test_bench_gpus_n_runs_n_ranks(n):
     cuda:0 (WGCS_DIST_BACKEND=gloo), one complete result line (cfg5_strong,
     cpu_baseline, every rank's kernel time)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "5",
-                        "--warmup", "2", "--cpu-seconds", "0.5", "--no-e2e"], cwd=ROOT,
+                        "--warmup", "2", "--full", "--cpu-seconds", "0.5", "--no-e2e"], cwd=ROOT,
                        env=_env(WGCS_DIST_BACKEND="gloo"), capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -255,7 +256,7 @@ def test_bench_default_line_complete():
     bench.line_problems accepts, with the kernel no slower than the wall clock
     allows."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5",
-                        "--warmup", "2", "--cpu-seconds", "0.5", "--no-e2e"], cwd=ROOT,
+                        "--warmup", "2", "--full", "--cpu-seconds", "0.5", "--no-e2e"], cwd=ROOT,
                        env=_env(), capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -283,3 +284,61 @@ def test_gate_streams_helper():
         d = Dev()
         got = bench.gate_streams(d, object(), ["s0", "s1", "s2"], use_events)
         assert got == want and [c[0] for c in d.calls] == want and all(c[1] == 1 for c in d.calls)
+
+
+def test_dump_outputs_files(tmp_path):
+    """bench.dump_outputs (--dump-outputs): VALIDATE's one byte per packet and
+    L4_FILL's 16-bit words go out as float32, n values, one file per rank at
+    N > 1; the bytes of the buffer past the n results are left out."""
+    import numpy as np
+
+    from wireguard_amd.tun import MODE_L4_FILL, MODE_VALIDATE
+
+    buf = np.full(10, 0xA5, np.uint8)
+    buf[:5] = [1, 0, 1, 1, 0]
+    p = bench.dump_outputs(str(tmp_path / "d"), MODE_VALIDATE, buf, 5, 0, 1)
+    assert os.path.basename(p) == "checksum_valid.npy"
+    got = np.load(p)
+    assert got.dtype == np.float32 and got.tolist() == [1, 0, 1, 1, 0]
+    words = np.array([0, 1, 0xFFFF, 0x1234, 0xA5A5], np.uint16)
+    p = bench.dump_outputs(str(tmp_path / "d"), MODE_L4_FILL, words.view(np.uint8), 4, 3, 8)
+    assert os.path.basename(p) == "l4_checksum_rank3.npy"
+    got = np.load(p)
+    assert got.dtype == np.float32 and got.tolist() == [0, 1, 0xFFFF, 0x1234]
+
+
+def test_dump_outputs_needs_a_checksum_config(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg4", "--dump-outputs",
+                        str(tmp_path / "d")], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr
+    assert not r.stdout.strip() and not (tmp_path / "d").exists()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps(tmp_path):
+    """A plain run (no --full): the line carries the headline keys and the
+    figures read off the timed steps' own events, and none of the legs that
+    take runs of their own; --dump-outputs writes the last timed step's
+    results (every synthetic frame is valid: 65,536 ones; a step that had not
+    written them would leave the 0xA5 fill)."""
+    import numpy as np
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5",
+                        "--warmup", "2", "--dump-outputs", str(tmp_path)], cwd=ROOT,
+                       env=_env(), capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = lines[0]
+    assert all(k in line for k in bench.REQUIRED_KEYS)
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["dtype"] == "u8" and line["higher_is_better"] is True
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    # value and ms_per_step are the same measurement: 65,536 x 1500 B per step
+    assert abs(line["value"] - 65536 * 1500 / (line["ms_per_step"] * 1e-3) / 2**30) <= 0.01 * line["value"]
+    assert line["roofline"]["kernel_ms"] <= line["ms_per_step"] * 1.05
+    for k in ("cpu_baseline", "cfg5_strong", "end_to_end", "host_call"):
+        assert k not in line, k
+    assert "kernel_ms_one_stream" not in line["roofline"] and "ungated" not in line["timing"]
+    assert sorted(os.listdir(tmp_path)) == ["checksum_valid.npy"]
+    got = np.load(tmp_path / "checksum_valid.npy")
+    assert got.dtype == np.float32 and got.shape == (65536,) and bool((got == 1.0).all())
