@@ -10,6 +10,7 @@
 //      through the BAR (the GPU polls its own HBM)
 // against a plain launch + hipStreamSynchronize of the same work.  Exit: a
 // stop word or an s_memrealtime deadline (every wave reaches it).
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 scripts/probe_ring.hip -o scripts/probe_so/probe_ring
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -1,6 +1,7 @@
 // api.cpp -- C ABI (include/wgcsum.h): context, staging and the
 // reference-shaped host entry points.  All per-byte work is done by the
-// gfx950 kernels in checksum_kernels.hip / gso_kernels.hip; there is no CPU
+// gfx950 kernels in checksum_kernels.hip / gso_kernels.hip (device code shared
+// with the resident ring: gso_device.h); there is no CPU
 // fallback: if HIP or the device is unavailable every call fails loudly.
 #include <hip/hip_runtime.h>
 

@@ -4,10 +4,10 @@
 // wgcs_handle_virtio_read) pay one kernel launch plus one completion wait per
 // Go call -- ~20 us on MI355X, more than the Go code of one Tun.Read
 // (INTEGRATION.md §2.0).  A ring keeps ring_kernel
-// (gso_kernels.hip) resident on a few CUs of its own stream; a call fills the
+// (ring_kernels.hip) resident on a few CUs of its own stream; a call fills the
 // request record in fine-grained pinned host memory, publishes it by storing
-// the request number last, and spins on the completion word the workgroups
-// bump after a system-scope release of their results.  Same arguments, bytes
+// the request number last, and spins on the completion records the workgroups
+// write after a system-scope release of their results.  Same arguments, bytes
 // and errors as the per-call forms (tun/gro.go:554-612, tun/tun.go:514-632);
 // only the transport differs.
 //
@@ -275,17 +275,6 @@ int wgcs_ring_info(wgcs_ring* rg, uint64_t* requests, uint64_t* launches, int* r
   if (running) *running = hipStreamQuery(rg->stream) == hipErrorNotReady ? 1 : 0;
   return WGCS_OK;
 }
-
-#ifdef WGCS_RING_STAMPS
-// probe builds only (not in include/wgcsum.h): the last request's phase stamps
-// of workgroup b, 4 words (ring_kernel, WGCS_RING_STAMPS)
-int wgcs_ring_debug_stamps(wgcs_ring* rg, int b, uint32_t* out) {
-  if (!rg || b < 0 || b >= (int)wgcs::kRingMaxBlocks || !out) return WGCS_ERR_INVALID_ARG;
-  const volatile uint32_t* d = reinterpret_cast<const volatile uint32_t*>(&rg->ctl->dn[b]);
-  for (int i = 0; i < 4; ++i) out[i] = d[4 + i];
-  return WGCS_OK;
-}
-#endif
 
 // checksumValid through the ring: wgcs_checksum_valid_cap's arguments and errors.
 int wgcs_ring_checksum_valid_cap(wgcs_ring* rg, const uint8_t* pkt, size_t len, size_t cap, uint8_t iph_len,

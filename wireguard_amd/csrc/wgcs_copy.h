@@ -16,7 +16,8 @@ namespace wgcs {
 // trips), so the compiler keeps them in the global address space and emits
 // global_load/store (not flat_*, which forces full vmcnt+lgkmcnt waits).
 //
-// WGCS_RING_TU (ring_kernels.hip, the resident per-call ring): the request
+// WGCS_RING_TU (defined by ring_kernels.hip, the resident per-call ring,
+// before it includes gso_device.h; it decides load scope only): the request
 // bytes change between requests at one address while the kernel stays
 // resident, so every load of them is a system-scope one (relaxed atomic: sc0
 // sc1, it misses the CU's L1 and the L2 -- no stale line of an earlier

@@ -42,7 +42,7 @@ struct GsoOutPos {
   uint32_t pitch;
   uint32_t flags;  // kOutPosTails
 };
-// The resident per-call ring (ring.cpp, ring_kernel in gso_kernels.hip): one
+// The resident per-call ring (ring.cpp, ring_kernel in ring_kernels.hip): one
 // request record the host fills and then publishes by storing `seq` last, and
 // the device's completion record on a line of its own; both in fine-grained
 // (coherent) pinned host memory.

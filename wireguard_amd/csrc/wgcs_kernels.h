@@ -13,7 +13,7 @@ hipError_t launch_checksum_batch(int mode, unsigned flags, uint8_t* arena, const
                                  const uint64_t* init, uint32_t n, void* out, hipStream_t s, int num_cu,
                                  const LaunchTuning& tune);
 
-// the resident per-call ring (gso_kernels.hip): nb workgroups serve the
+// the resident per-call ring (ring_kernels.hip): nb workgroups serve the
 // requests of ctl (coherent pinned host memory) until its stop word or
 // idle_ticks (100 MHz) without a request
 hipError_t launch_ring(RingCtl* ctl, uint32_t nb, uint32_t last, uint64_t idle_ticks, hipStream_t s);
