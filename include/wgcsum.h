@@ -68,7 +68,8 @@ extern "C" {
 #define WGCS_ERR_NOT_READY (-15)        /* stager: batch id not submitted / recycled */
 #define WGCS_ERR_CMSG (-16)             /* "error parsing socket control message: %w" conn/gso.go:45 */
 #define WGCS_ERR_SPLIT_OVERFLOW (-17)   /* "splitting coalesced packet resulted in overflow" conn/bind.go:565 */
-#define WGCS_ERR_HIP (-100)             /* HIP runtime error (message: wgcs_last_error) */
+#define WGCS_ERR_AUTH (-18)             /* "chacha20poly1305: message authentication failed" receive.go:380 */
+#define WGCS_ERR_HIP (-100)            /* HIP runtime error (message: wgcs_last_error) */
 #define WGCS_ERR_NOMEM (-101)
 #define WGCS_ERR_NO_DEVICE (-102)
 
@@ -484,6 +485,84 @@ int wgcs_coalesce_messages(wgcs_ctx *ctx, uint8_t *const *bufs, const size_t *le
                            int nbufs, int dst_is_v6, const uint8_t *src_ctl, size_t src_len,
                            uint8_t *const *oobs, size_t *oob_lens, const size_t *oob_caps,
                            int *msg_first, size_t *msg_len, int *n_msgs);
+
+/* ---- transport AEAD (device/send.go:438-463, device/receive.go:363-383, :432-482)
+ * ChaCha20-Poly1305 (RFC 8439) with empty additional data and the nonce
+ * 4 zero bytes | LE64 counter, on transport messages
+ *   LE32 type 4 | LE32 receiver index | LE64 counter | ciphertext | 16-byte tag.
+ * Batches work in place on packets at any byte offset of one arena. */
+
+/* One session key in device memory (4-byte aligned).  The table is the
+ * caller's: clear or overwrite it on rekey. */
+typedef struct wgcs_aead_key {
+  uint8_t key[32];
+  uint32_t remote_index; /* SEAL: the receiver index written into the header */
+  uint32_t pad[3];
+} wgcs_aead_key; /* 48 B */
+
+/* One packet: SEAL  plaintext of len bytes at off + 16, sealed under
+ *                   (keys[key], counter); room for the header before it and
+ *                   for padding and tag after it;
+ *             OPEN  the whole transport message of len bytes at off (counter
+ *                   is not read: it comes from message bytes [8, 16)). */
+typedef struct wgcs_aead_pkt {
+  uint64_t off;
+  uint64_t counter;
+  uint32_t len;
+  uint32_t key;
+} wgcs_aead_pkt; /* 24 B, 8-byte aligned */
+
+/* padding(packetSize, mtu) of send.go:529-560 (host only): the zero bytes
+ * RoutineEncryption appends (never negative). */
+int wgcs_padding(size_t packet_size, uint32_t mtu);
+
+/* RoutineEncryption's per-packet work for n packets, asynchronous on stream
+ * (NULL: the context's).  Per packet i, with padded = len + padding(len, mtu):
+ * writes the header at [off, off + 16), reads the plaintext [off + 16,
+ * off + 16 + len), writes ciphertext and tag at [off + 16, off + 32 + padded)
+ * (it may read any byte of that range first), and sets d_out_len[i] =
+ * 32 + padded.  So the arena must be readable and writable through
+ * off + 32 + padded, and no byte outside [off, off + 32 + padded) is written.
+ * d_out_len[i] = WGCS_ERR_OUT_OF_RANGE if len > 65535, WGCS_ERR_INVALID_ARG if
+ * key >= n_keys; such a packet's bytes are neither read nor written.  n == 0
+ * is a no-op. */
+int wgcs_aead_seal_batch(wgcs_ctx *ctx, uint8_t *d_arena, const wgcs_aead_pkt *d_pkts,
+                         const wgcs_aead_key *d_keys, uint32_t n_keys, uint32_t n, uint32_t mtu,
+                         int32_t *d_out_len, void *stream);
+
+/* RoutineDecryption's per-packet work plus the length trim of
+ * RoutineSendToInternet, asynchronous on stream.  Per packet i it reads the
+ * message [off, off + len) and writes only inside [off + 16, off + len - 16):
+ * the plaintext, in place, when the tag matches, else zeros -- this ABI's
+ * contract for what Open leaves of a rejected message; header and tag stay as
+ * they were.  d_counter[i] = the counter field (the replay filter and the
+ * allowed-source check stay with the caller).  d_pkt_len[i] =
+ *   WGCS_ERR_AUTH              the tag does not match             receive.go:380-383
+ *   0                          keepalive (empty plaintext)        :432
+ *   the IPv4 total length      if 20 <= it <= plaintext length    :440-449
+ *   the IPv6 payload length + 40 in uint16 arithmetic, if <= plaintext length  :460-470
+ *   WGCS_ERR_PACKET_TOO_SHORT  any other version nibble, a plaintext shorter
+ *                              than its IP header, a length out of range
+ *   WGCS_ERR_OUT_OF_RANGE      len < 32 or len > 65535  } nothing read or written,
+ *   WGCS_ERR_INVALID_ARG       key >= n_keys            } d_counter[i] = 0
+ * n == 0 is a no-op. */
+int wgcs_aead_open_batch(wgcs_ctx *ctx, uint8_t *d_arena, const wgcs_aead_pkt *d_pkts,
+                         const wgcs_aead_key *d_keys, uint32_t n_keys, uint32_t n, int32_t *d_pkt_len,
+                         uint64_t *d_counter, void *stream);
+
+/* One packet from host memory through the same kernel (staged in device
+ * memory; one launch, one wait).  buf[0:16) is the header room, buf[16:16+len)
+ * the packet, cap the size of buf; *out_len = 32 + len + padding(len, mtu).
+ * WGCS_ERR_OUT_OF_RANGE if len > 65535 or cap < *out_len (buf untouched). */
+int wgcs_aead_seal(wgcs_ctx *ctx, const uint8_t key[32], uint32_t remote_index, uint64_t counter,
+                   uint8_t *buf, size_t len, size_t cap, uint32_t mtu, size_t *out_len);
+/* msg[0:len) is a transport message.  Returns WGCS_OK with the plaintext in
+ * msg[16:len-16) and *pkt_len = its trimmed length (0: keepalive), or
+ * WGCS_ERR_PACKET_TOO_SHORT likewise decrypted, or WGCS_ERR_AUTH with that
+ * range zeroed, or WGCS_ERR_OUT_OF_RANGE (len < 32 or > 65535, msg untouched).
+ * *counter = the counter field unless out of range. */
+int wgcs_aead_open(wgcs_ctx *ctx, const uint8_t key[32], uint8_t *msg, size_t len, uint64_t *counter,
+                   int *pkt_len);
 
 #ifdef __cplusplus
 }

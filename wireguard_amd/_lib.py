@@ -33,6 +33,7 @@ ERR_BATCH_FULL = -14
 ERR_NOT_READY = -15
 ERR_CMSG = -16
 ERR_SPLIT_OVERFLOW = -17
+ERR_AUTH = -18
 ERR_HIP = -100
 ERR_NOMEM = -101
 ERR_NO_DEVICE = -102
@@ -53,6 +54,14 @@ class VirtioHdr(C.Structure):
         ("flags", C.c_uint8), ("gso_type", C.c_uint8), ("hdr_len", C.c_uint16),
         ("gso_size", C.c_uint16), ("csum_start", C.c_uint16), ("csum_offset", C.c_uint16),
     ]
+
+
+class AeadKey(C.Structure):  # wgcs_aead_key
+    _fields_ = [("key", C.c_uint8 * 32), ("remote_index", C.c_uint32), ("pad", C.c_uint32 * 3)]
+
+
+class AeadPkt(C.Structure):  # wgcs_aead_pkt
+    _fields_ = [("off", C.c_uint64), ("counter", C.c_uint64), ("len", C.c_uint32), ("key", C.c_uint32)]
 
 
 _lib = None
@@ -147,6 +156,11 @@ def load() -> C.CDLL:
         "wgcs_wstager_wait": ([vp, u64], i32),
         "wgcs_wstager_result": ([vp, u64, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(vp),
                                  C.POINTER(sz)], i32),
+        "wgcs_padding": ([sz, u32], i32),
+        "wgcs_aead_seal_batch": ([vp, vp, vp, vp, u32, u32, u32, vp, vp], i32),
+        "wgcs_aead_open_batch": ([vp, vp, vp, vp, u32, u32, vp, vp, vp], i32),
+        "wgcs_aead_seal": ([vp, vp, u32, u64, vp, sz, sz, u32, C.POINTER(sz)], i32),
+        "wgcs_aead_open": ([vp, vp, vp, sz, C.POINTER(u64), C.POINTER(i32)], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

@@ -45,4 +45,10 @@ hipError_t launch_udp_coalesce(uint8_t* bufs, uint64_t stride, uint32_t buf_cap,
                                int dst_is_v6, int32_t* n_msgs, int32_t* msg_first, int32_t* msg_len,
                                int32_t* msg_gso, hipStream_t s);
 
+// Transport AEAD, in place (aead_kernels.hip): open != 0 is Open (out_ctr
+// required, mtu unused), else Seal.
+hipError_t launch_aead_batch(int open, uint8_t* arena, const wgcs_aead_pkt* pkts, const wgcs_aead_key* keys,
+                             uint32_t n_keys, uint32_t n, uint32_t mtu, int32_t* out_len, uint64_t* out_ctr,
+                             hipStream_t s);
+
 }  // namespace wgcs
