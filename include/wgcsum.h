@@ -33,6 +33,12 @@
  *   wgcs_split_messages_batch device-resident batch of splitMessages calls (one per recvmmsg)
  *   wgcs_coalesce_messages    coalesceMessages(msgs, bufs, ep, addr)  conn/bind.go:599-662
  *   wgcs_coalesce_messages_batch  device-resident batch of coalesceMessages calls (one per Send)
+ *   wgcs_aead_*               transport-message Seal / Open       device/send.go:438-463, device/receive.go:363-383
+ *   wgcs_router_*             Router (allowed-IPs trie)           device/router.go:405-495
+ *   wgcs_session_table_build  SessionMap.Get as an array          device/sessions.go:26-30
+ *   wgcs_recv_classify_batch  the loop body of RoutineReceiveFromPeers   device/receive.go:145-207
+ *   wgcs_recv_source_batch    the allowed-source check            device/receive.go:438-482
+ *   wgcs_route_dst_batch      the routing step of RoutineReadFromTUN     device/send.go:264-293
  *   wgcs_stager_*             Tun.Read batch staging              tun/tun.go:477-508
  *   wgcs_wstager_*            Tun.Write batch staging             tun/tun.go:654-700
  * Status codes map 1:1 onto the reference's Go errors (see WGCS_ERR_*).
@@ -69,7 +75,8 @@ extern "C" {
 #define WGCS_ERR_CMSG (-16)             /* "error parsing socket control message: %w" conn/gso.go:45 */
 #define WGCS_ERR_SPLIT_OVERFLOW (-17)   /* "splitting coalesced packet resulted in overflow" conn/bind.go:565 */
 #define WGCS_ERR_AUTH (-18)             /* "chacha20poly1305: message authentication failed" receive.go:380 */
-#define WGCS_ERR_HIP (-100)            /* HIP runtime error (message: wgcs_last_error) */
+#define WGCS_ERR_SOURCE (-19)           /* "packet with disallowed source address" receive.go:452-457, :472-477 */
+#define WGCS_ERR_HIP (-100)           /* HIP runtime error (message: wgcs_last_error) */
 #define WGCS_ERR_NOMEM (-101)
 #define WGCS_ERR_NO_DEVICE (-102)
 
@@ -535,8 +542,8 @@ int wgcs_aead_seal_batch(wgcs_ctx *ctx, uint8_t *d_arena, const wgcs_aead_pkt *d
  * message [off, off + len) and writes only inside [off + 16, off + len - 16):
  * the plaintext, in place, when the tag matches, else zeros -- this ABI's
  * contract for what Open leaves of a rejected message; header and tag stay as
- * they were.  d_counter[i] = the counter field (the replay filter and the
- * allowed-source check stay with the caller).  d_pkt_len[i] =
+ * they were.  d_counter[i] = the counter field (the replay filter stays with
+ * the caller; the allowed-source check is wgcs_recv_source_batch).  d_pkt_len[i] =
  *   WGCS_ERR_AUTH              the tag does not match             receive.go:380-383
  *   0                          keepalive (empty plaintext)        :432
  *   the IPv4 total length      if 20 <= it <= plaintext length    :440-449
@@ -563,6 +570,114 @@ int wgcs_aead_seal(wgcs_ctx *ctx, const uint8_t key[32], uint32_t remote_index, 
  * *counter = the counter field unless out of range. */
 int wgcs_aead_open(wgcs_ctx *ctx, const uint8_t key[32], uint8_t *msg, size_t len, uint64_t *counter,
                    int *pkt_len);
+
+/* ---- peer lookup: allowed-IPs router and session table (device/router.go,
+ * device/sessions.go) ----
+ * The two data-dependent lookups of the per-packet path: Router.Find on a
+ * packet's source or destination address and SessionMap.Get on a transport
+ * message's receiver index.  The host keeps the trie (insert / remove as the
+ * reference does) and writes a flat image of it; the caller copies the image
+ * and the session slots to device memory, as it does the AEAD key table, and
+ * the three batch entry points below read them there. */
+
+#define WGCS_PEER_NONE 0xFFFFFFFFu /* Find's nil; never a peer id */
+
+/* Router (router.go:405-495) with caller-chosen uint32 peer ids in place of
+ * *Peer.  No context and no device; writers and readers are guarded as the
+ * reference's RWMutex guards them.  addr_len is 4 or 16. */
+typedef struct wgcs_router wgcs_router;
+typedef struct wgcs_prefix {
+  uint8_t addr[16]; /* masked to cidr; IPv4 in addr[0:4) */
+  uint8_t addr_len; /* 4 or 16 */
+  uint8_t cidr;
+  uint8_t pad[2];
+} wgcs_prefix; /* 20 B */
+wgcs_router *wgcs_router_create(void);
+void wgcs_router_destroy(wgcs_router *r);
+/* Router.Insert (:411-424); the address is masked to cidr (maskSelf, :126-139).
+ * INVALID_ARG for an addr_len other than 4 or 16 (the reference panics),
+ * cidr > 8 * addr_len or peer == WGCS_PEER_NONE; WGCS_ERR_NOMEM. */
+int wgcs_router_insert(wgcs_router *r, const uint8_t *addr, size_t addr_len, uint8_t cidr, uint32_t peer);
+/* Router.Remove (:439-457): a no-op unless exactly this prefix is present and is peer's */
+int wgcs_router_remove(wgcs_router *r, const uint8_t *addr, size_t addr_len, uint8_t cidr, uint32_t peer);
+/* Router.RemoveByPeer (:460-478) */
+int wgcs_router_remove_by_peer(wgcs_router *r, uint32_t peer);
+/* Router.Find (:426-437): the peer of the longest matching prefix, or
+ * WGCS_PEER_NONE (also for a NULL argument or an addr_len other than 4 or 16) */
+uint32_t wgcs_router_find(wgcs_router *r, const uint8_t *addr, size_t addr_len);
+/* Router.PeerNodes (:481-495): *n = how many prefixes peer has, the first
+ * min(*n, cap) of them in out, in the order of the reference's peer.nodes list
+ * (insertion order; an exact re-insert moves the prefix to the back) */
+int wgcs_router_peer_prefixes(wgcs_router *r, uint32_t peer, wgcs_prefix *out, size_t cap, size_t *n);
+/* A flat, position-independent image of both tries: image_size bytes now;
+ * write_image fills buf (cap bytes; OUT_OF_RANGE if too small) and sets *len.
+ * The format is private to the library.  The device copy must be 16-byte
+ * aligned and stays the caller's: write a new image after the router changes. */
+size_t wgcs_router_image_size(wgcs_router *r);
+int wgcs_router_write_image(wgcs_router *r, uint8_t *buf, size_t cap, size_t *len);
+/* Find on an image in host memory (any alignment), the walk the kernels run.
+ * INVALID_ARG (*peer = WGCS_PEER_NONE) for bytes that are not an image. */
+int wgcs_router_image_find(const uint8_t *buf, size_t len, const uint8_t *addr, size_t addr_len, uint32_t *peer);
+
+/* SessionMap.Get (sessions.go:26-30) as an open-addressed array the caller
+ * uploads: slot.key is the session's row in the AEAD key table.  List only
+ * sessions that have a keypair (keypair == nil is "not found",
+ * receive.go:164-166) and whose keypair has not expired (:168 is host
+ * wall-clock state). */
+typedef struct wgcs_session_slot {
+  uint32_t index; /* the receiver index */
+  uint32_t key;   /* 0xFFFFFFFF: the slot is empty */
+} wgcs_session_slot;
+/* n_slots: a power of two, >= 2 * n and >= 1.  INVALID_ARG for any other
+ * n_slots, a key of 0xFFFFFFFF or an index listed twice. */
+int wgcs_session_table_build(const uint32_t *indices, const uint32_t *keys, uint32_t n, wgcs_session_slot *slots,
+                             uint32_t n_slots);
+
+/* The three batch entry points: ordinary launches, asynchronous on stream
+ * (NULL: the context's), n <= 2^28, n == 0 a no-op.  They read the arena and
+ * never write it; packets and addresses may sit at any byte offset.
+ *
+ * The loop body of RoutineReceiveFromPeers (receive.go:145-207).  Message q of
+ * d_size[q] bytes is at d_off[q], or at q * stride when d_off is NULL (what
+ * wgcs_split_messages_batch writes, with its d_n_out as d_size).  d_type[q] =
+ *   0                     size < 32 (nothing read); a handshake type whose
+ *                         size is not its own; a transport message whose
+ *                         receiver index is not in the table; any other LE32 type
+ *   1, 2, 3               initiation of 148 B, response of 92 B, cookie reply of 64 B
+ *   4                     a transport message of a listed session
+ *   WGCS_ERR_OUT_OF_RANGE size > 65535, or size > stride in the strided form
+ *                         (nothing read)
+ * and d_pkts[q] = {off, 0, size, key}: key = the session's key for type 4, else
+ * 0xFFFFFFFF, which wgcs_aead_open_batch refuses without touching the row; len
+ * is 0 for a negative d_type.  d_slots is 4-byte, d_pkts 8-byte aligned. */
+int wgcs_recv_classify_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const uint64_t *d_off, uint64_t stride,
+                             const int32_t *d_size, uint32_t n, const wgcs_session_slot *d_slots,
+                             uint32_t n_slots, wgcs_aead_pkt *d_pkts, int32_t *d_type, void *stream);
+
+/* The allowed-source check of RoutineSendToInternet (receive.go:438-482) on
+ * what wgcs_aead_open_batch left.  d_pkt_len[i] <= 0 (a keepalive, any error)
+ * passes through to d_verdict[i] with nothing read.  Else the packet is
+ * d_pkt_len[i] bytes at d_pkts[i].off + 16: IPv4 of >= 20 B has its source at
+ * [12, 16), IPv6 of >= 40 B at [8, 24), anything else is
+ * WGCS_ERR_PACKET_TOO_SHORT.  d_verdict[i] = the length if Find(source) ==
+ * d_key_peer[d_pkts[i].key], else WGCS_ERR_SOURCE (no route is a mismatch);
+ * WGCS_ERR_INVALID_ARG for key >= n_keys or an image that is not one.
+ * d_peer (optional) receives Find(source), WGCS_PEER_NONE where none was
+ * looked up.  d_verdict may alias d_pkt_len.  d_image is 16-byte aligned. */
+int wgcs_recv_source_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgcs_aead_pkt *d_pkts,
+                           const int32_t *d_pkt_len, const uint32_t *d_key_peer, uint32_t n_keys, uint32_t n,
+                           const uint8_t *d_image, size_t image_bytes, int32_t *d_verdict, uint32_t *d_peer,
+                           void *stream);
+
+/* The routing step of RoutineReadFromTUN (send.go:264-293).  The packet of
+ * slot q, d_size[q] bytes, starts at (d_off ? d_off[q] : q * stride) + offset
+ * (what wgcs_gso_split_batch writes with its offset, with its d_sizes).
+ * d_peer[q] = Find(dst) -- IPv4 of >= 20 B: bytes [16, 20), IPv6 of >= 40 B:
+ * [24, 40) -- or WGCS_PEER_NONE for size < 1, a shorter packet, any other
+ * version nibble, no route or an image that is not one. */
+int wgcs_route_dst_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const uint64_t *d_off, uint64_t stride,
+                         uint32_t offset, const int32_t *d_size, uint32_t n, const uint8_t *d_image,
+                         size_t image_bytes, uint32_t *d_peer, void *stream);
 
 #ifdef __cplusplus
 }

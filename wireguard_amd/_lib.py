@@ -34,6 +34,7 @@ ERR_NOT_READY = -15
 ERR_CMSG = -16
 ERR_SPLIT_OVERFLOW = -17
 ERR_AUTH = -18
+ERR_SOURCE = -19
 ERR_HIP = -100
 ERR_NOMEM = -101
 ERR_NO_DEVICE = -102
@@ -41,6 +42,7 @@ ERR_NO_DEVICE = -102
 MODE_FOLD, MODE_L4_FILL, MODE_VALIDATE, MODE_PARTIAL, MODE_IP4HDR = 0, 1, 2, 3, 4
 F_INPLACE = 0x1
 PKT_V6 = 0x01
+PEER_NONE = 0xFFFFFFFF  # Router.Find's nil
 
 
 class WgcsError(RuntimeError):
@@ -161,6 +163,20 @@ def load() -> C.CDLL:
         "wgcs_aead_open_batch": ([vp, vp, vp, vp, u32, u32, vp, vp, vp], i32),
         "wgcs_aead_seal": ([vp, vp, u32, u64, vp, sz, sz, u32, C.POINTER(sz)], i32),
         "wgcs_aead_open": ([vp, vp, vp, sz, C.POINTER(u64), C.POINTER(i32)], i32),
+        "wgcs_router_create": ([], vp),
+        "wgcs_router_destroy": ([vp], None),
+        "wgcs_router_insert": ([vp, vp, sz, C.c_uint8, u32], i32),
+        "wgcs_router_remove": ([vp, vp, sz, C.c_uint8, u32], i32),
+        "wgcs_router_remove_by_peer": ([vp, u32], i32),
+        "wgcs_router_find": ([vp, vp, sz], u32),
+        "wgcs_router_peer_prefixes": ([vp, u32, vp, sz, C.POINTER(sz)], i32),
+        "wgcs_router_image_size": ([vp], sz),
+        "wgcs_router_write_image": ([vp, vp, sz, C.POINTER(sz)], i32),
+        "wgcs_router_image_find": ([vp, sz, vp, sz, C.POINTER(u32)], i32),
+        "wgcs_session_table_build": ([vp, vp, u32, vp, u32], i32),
+        "wgcs_recv_classify_batch": ([vp, vp, vp, u64, vp, u32, vp, u32, vp, vp, vp], i32),
+        "wgcs_recv_source_batch": ([vp, vp, vp, vp, vp, u32, u32, vp, sz, vp, vp, vp], i32),
+        "wgcs_route_dst_batch": ([vp, vp, vp, u64, u32, vp, u32, vp, sz, vp, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

@@ -51,4 +51,17 @@ hipError_t launch_aead_batch(int open, uint8_t* arena, const wgcs_aead_pkt* pkts
                              uint32_t n_keys, uint32_t n, uint32_t mtu, int32_t* out_len, uint64_t* out_ctr,
                              hipStream_t s);
 
+// Peer lookup (route_kernels.hip): receive classification against the session
+// slots, the allowed-source check and destination routing against a router
+// image (wgcs_route_walk.h).  off == nullptr: slot q at q * stride.
+hipError_t launch_recv_classify(const uint8_t* arena, const uint64_t* off, uint64_t stride, const int32_t* sizes,
+                                uint32_t n, const wgcs_session_slot* slots, uint32_t n_slots, wgcs_aead_pkt* pkts,
+                                int32_t* types, hipStream_t s);
+hipError_t launch_recv_source(const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* pkt_len,
+                              const uint32_t* key_peer, uint32_t n_keys, uint32_t n, const uint8_t* image,
+                              uint64_t image_bytes, int32_t* verdict, uint32_t* peer, hipStream_t s);
+hipError_t launch_route_dst(const uint8_t* arena, const uint64_t* off, uint64_t stride, uint32_t offset,
+                            const int32_t* sizes, uint32_t n, const uint8_t* image, uint64_t image_bytes,
+                            uint32_t* peer, hipStream_t s);
+
 }  // namespace wgcs
