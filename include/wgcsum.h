@@ -223,6 +223,9 @@ int wgcs_stream_wait_flag(wgcs_ctx *ctx, void *stream, const uint32_t *flag, uin
  * (like bufs[s][offset:]).  d_sizes[slot] = packet size; d_count[j] = the
  * return value n (>= 0) and d_status[j] = 0 or a WGCS_ERR_* code, with the
  * reference's ErrTooManySegments semantics (n = max_segs-1, gro.go:1409-1410).
+ * d_sizes is written for the slots the job reaches only (d_count[j] of them;
+ * all max_segs with TOO_MANY_SEGMENTS); the other rows and slots keep what
+ * they held.
  * Includes handleVirtioRead's GSO validation (tun/tun.go:557-631).
  * INVALID_ARG for max_segs == 0, max_segs >= 2^31 (len(bufs) is a Go int) or
  * n_jobs * max_segs >= 2^32. */
@@ -454,7 +457,13 @@ int wgcs_set_gso_size(uint8_t *control, size_t *len, size_t cap, uint16_t gso_si
  * d_count[b] = nPackets, d_status[b] = 0 / WGCS_ERR_CMSG / WGCS_ERR_SPLIT_OVERFLOW /
  * WGCS_ERR_OUT_OF_RANGE (Buffers[0][0:gsoSize] beyond cap) / WGCS_ERR_INVALID_ARG
  * (N > buf_len or a packet larger than out_stride).  On an error status the
- * packets before it are written, as the reference copies them before returning. */
+ * packets before it are written, as the reference copies them before returning.
+ * No byte of d_out outside [slot, slot + d_n_out) of the packets below d_count[b]
+ * is written: the rest of such a slot and every slot at or past d_count[b] keep
+ * what they held (d_n_out there is the d_n_in given: 0 for a pool message and
+ * for a source whose packets went elsewhere; d_src is -1).  d_in, d_n_in and
+ * d_gso are only read.  So wgcs_recv_classify_batch may run over all
+ * n_batches * n_msgs slots with d_n_out as its d_size. */
 int wgcs_split_messages_batch(wgcs_ctx *ctx, const uint8_t *d_in, uint64_t in_stride, uint32_t buf_len,
                               const int32_t *d_n_in, const int32_t *d_gso, uint32_t n_msgs,
                               uint32_t first_msg_at, uint32_t n_batches, uint8_t *d_out,
@@ -468,7 +477,13 @@ int wgcs_split_messages_batch(wgcs_ctx *ctx, const uint8_t *d_in, uint64_t in_st
  * Appends land in the first buffer of each run, as Go's append within cap does.
  * Per batch: d_n_msgs[b] = nMsgs; per message m (index b*max_bufs + m):
  * d_msg_first = the buffer j that msgs[m].Buffers[0] aliases, d_msg_len = its
- * final length, d_msg_gso = the UDP_SEGMENT size set by setGSOSize, or -1 if none. */
+ * final length, d_msg_gso = the UDP_SEGMENT size set by setGSOSize, or -1 if none.
+ * No byte of d_bufs outside [0, cap) of a batch's first d_nbufs[b] buffers is
+ * written: what lies between a buffer's capacity and its slot's end, and the
+ * slots at or past d_nbufs[b], keep what they held.  d_lens and d_caps are read
+ * below d_nbufs[b] only, so the rows past it may hold anything (with
+ * wgcs_aead_seal_batch's d_out_len as d_lens: its negative refusals, or rows it
+ * never wrote); the message rows at or past d_n_msgs[b] are not written. */
 int wgcs_coalesce_messages_batch(wgcs_ctx *ctx, uint8_t *d_bufs, uint64_t buf_stride, uint32_t buf_cap,
                                  const int32_t *d_caps, const int32_t *d_lens, const int32_t *d_nbufs,
                                  uint32_t max_bufs, uint32_t n_batches, int dst_is_v6, int32_t *d_n_msgs,

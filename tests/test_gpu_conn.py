@@ -4,7 +4,12 @@ N, Addr, nPackets / nMsgs, status code and control message.
 
 Host-call API (wgcs_split_messages / wgcs_coalesce_messages) on seeded random
 recvmmsg / Send batches, then the device-resident batch API on many batches
-at once, compared batch by batch."""
+at once, compared batch by batch.  The batch tests fill the output arena with
+a sentinel and the output arrays with a marker and compare every slot over its
+whole stride: both kernels end packets with partial 16-byte chunks, and a store
+past a packet's end, past a buffer's capacity or into a slot at or past
+d_count / d_nbufs must show (in the chains of INTEGRATION §2g / §2h that slack
+is the next stage's input or spare capacity)."""
 import numpy as np
 import pytest
 
@@ -85,6 +90,10 @@ def _split_batch_ref(msgs_list, first):
     return outs
 
 
+SENTINEL = 0xC3  # under every output byte a kernel may not write
+MARK = 12345     # in every output row before the launch
+
+
 def _split_batch_check(dev, cases, n_msgs, first, buf_len, in_stride):
     import torch
 
@@ -104,11 +113,11 @@ def _split_batch_check(dev, cases, n_msgs, first, buf_len, in_stride):
     d_in = torch.from_numpy(h_in).cuda()
     d_n = torch.from_numpy(n_in).cuda()
     d_g = torch.from_numpy(gso).cuda()
-    d_out = torch.zeros((B * n_msgs, out_stride), dtype=torch.uint8, device="cuda")
-    d_nout = torch.zeros(B * n_msgs, dtype=torch.int32, device="cuda")
-    d_src = torch.zeros(B * n_msgs, dtype=torch.int32, device="cuda")
-    d_cnt = torch.zeros(B, dtype=torch.int32, device="cuda")
-    d_st = torch.zeros(B, dtype=torch.int32, device="cuda")
+    d_out = torch.full((B * n_msgs, out_stride), SENTINEL, dtype=torch.uint8, device="cuda")
+    d_nout = torch.full((B * n_msgs,), MARK, dtype=torch.int32, device="cuda")
+    d_src = torch.full((B * n_msgs,), MARK, dtype=torch.int32, device="cuda")
+    d_cnt = torch.full((B,), MARK, dtype=torch.int32, device="cuda")
+    d_st = torch.full((B,), MARK, dtype=torch.int32, device="cuda")
     rc = dev.lib.wgcs_split_messages_batch(dev.h, d_in.data_ptr(), in_stride, buf_len, d_n.data_ptr(), d_g.data_ptr(),
                                            n_msgs, first, B, d_out.data_ptr(), out_stride, d_nout.data_ptr(),
                                            d_src.data_ptr(), d_cnt.data_ptr(), d_st.data_ptr(), None)
@@ -116,6 +125,8 @@ def _split_batch_check(dev, cases, n_msgs, first, buf_len, in_stride):
     dev.sync()
     out, nout, src = d_out.cpu().numpy(), d_nout.cpu().numpy(), d_src.cpu().numpy()
     cnt, st = d_cnt.cpu().numpy(), d_st.cpu().numpy()
+    # every slot in full: [0, n) is the packet, [n, out_stride) and every slot at or past count stay untouched
+    want = np.full_like(out, SENTINEL)
     for b, (npk, rco, mo) in enumerate(_split_batch_ref(cases, first)):
         assert (cnt[b], st[b]) == (npk, rco), b
         for k in range(n_msgs):
@@ -124,8 +135,14 @@ def _split_batch_check(dev, cases, n_msgs, first, buf_len, in_stride):
             if k < npk:
                 assert mo[k].addr == f"addr{src[q]}", (b, k)
                 assert np.array_equal(out[q, : mo[k].n], mo[k].buf[: mo[k].n]), (b, k)
+                want[q, : mo[k].n] = mo[k].buf[: mo[k].n]
             else:
                 assert src[q] == -1
+    if not np.array_equal(out, want):
+        q, x = (int(v[0]) for v in np.nonzero(out != want))
+        raise AssertionError(f"slot {q} (batch {q // n_msgs}, message {q % n_msgs}, n_out {nout[q]}, count "
+                             f"{cnt[q // n_msgs]}): byte {x} written, {int((out != want).sum())} such bytes in all")
+    assert np.array_equal(d_in.cpu().numpy(), h_in)  # the landing buffers are only read
 
 
 @pytest.mark.parametrize("seed,in_stride", [(0, 65536), (1, 65536), (2, 65536), (3, 65541), (4, 65664 + 56)])
@@ -175,7 +192,7 @@ def test_coalesce_messages_batch(dev, seed):
     B, max_bufs, stride = 12, 128, 65536
     cases = [coalesce_case(rng, nbufs=int(rng.integers(1, max_bufs + 1))) for _ in range(B)]
     v6 = bool(rng.integers(2))
-    h = np.zeros((B * max_bufs, stride), dtype=np.uint8)
+    h = np.full((B * max_bufs, stride), SENTINEL, dtype=np.uint8)  # under the buffers, between them and past them
     lens = np.zeros(B * max_bufs, dtype=np.int32)
     caps = np.zeros(B * max_bufs, dtype=np.int32)
     nb = np.zeros(B, dtype=np.int32)
@@ -188,8 +205,8 @@ def test_coalesce_messages_batch(dev, seed):
             caps[q] = len(buf)
     d = torch.from_numpy(h).cuda()
     d_lens, d_caps, d_nb = (torch.from_numpy(x).cuda() for x in (lens, caps, nb))
-    d_nm = torch.zeros(B, dtype=torch.int32, device="cuda")
-    d_first, d_len, d_gso = (torch.zeros(B * max_bufs, dtype=torch.int32, device="cuda") for _ in range(3))
+    d_nm = torch.full((B,), MARK, dtype=torch.int32, device="cuda")
+    d_first, d_len, d_gso = (torch.full((B * max_bufs,), MARK, dtype=torch.int32, device="cuda") for _ in range(3))
     rc = dev.lib.wgcs_coalesce_messages_batch(dev.h, d.data_ptr(), stride, 65535, d_caps.data_ptr(),
                                               d_lens.data_ptr(), d_nb.data_ptr(), max_bufs, B, int(v6),
                                               d_nm.data_ptr(), d_first.data_ptr(), d_len.data_ptr(),
@@ -198,6 +215,9 @@ def test_coalesce_messages_batch(dev, seed):
     dev.sync()
     got, nm = d.cpu().numpy(), d_nm.cpu().numpy()
     first, mlen, gso = d_first.cpu().numpy(), d_len.cpu().numpy(), d_gso.cpu().numpy()
+    # every slot over the whole stride: what lies between a buffer's capacity and the slot's end, and the
+    # slots at and past d_nbufs[b], must not change
+    want = h.copy()
     for b, (bufs, ln, src, _, _) in enumerate(cases):
         bo = [x.copy() for x in bufs]
         mo = [Msg(np.zeros(1, np.uint8), 64) for _ in bufs]
@@ -209,5 +229,14 @@ def test_coalesce_messages_batch(dev, seed):
             assert (first[q], mlen[q]) == (f, mo[m].buf_len), (b, m)
             g = int.from_bytes(mo[m].oob[16:18].tobytes(), "little") if mo[m].oob_len == 24 else -1
             assert gso[q] == g, (b, m)
+        for a in (first, mlen, gso):  # rows at or past n_msgs[b] keep the marker
+            assert (a[b * max_bufs + nmo: (b + 1) * max_bufs] == MARK).all(), b
         for j, x in enumerate(bo):
             assert np.array_equal(got[b * max_bufs + j, : len(x)], x), (b, j)
+            want[b * max_bufs + j, : len(x)] = x
+    if not np.array_equal(got, want):
+        q, x = (int(v[0]) for v in np.nonzero(got != want))
+        raise AssertionError(f"slot {q} (batch {q // max_bufs}, buffer {q % max_bufs} of {nb[q // max_bufs]}, cap "
+                             f"{caps[q]}): byte {x} written, {int((got != want).sum())} such bytes in all")
+    for x, hx in ((d_lens, lens), (d_caps, caps), (d_nb, nb)):
+        assert np.array_equal(x.cpu().numpy(), hx)
