@@ -76,6 +76,7 @@ extern "C" {
 #define WGCS_ERR_SPLIT_OVERFLOW (-17)   /* "splitting coalesced packet resulted in overflow" conn/bind.go:565 */
 #define WGCS_ERR_AUTH (-18)             /* "chacha20poly1305: message authentication failed" receive.go:380 */
 #define WGCS_ERR_SOURCE (-19)           /* "packet with disallowed source address" receive.go:452-457, :472-477 */
+#define WGCS_ERR_REPLAY (-20)           /* replayFilter.Validate said no: the packet is dropped  receive.go:418-420 */
 #define WGCS_ERR_HIP (-100)           /* HIP runtime error (message: wgcs_last_error) */
 #define WGCS_ERR_NOMEM (-101)
 #define WGCS_ERR_NO_DEVICE (-102)
@@ -693,6 +694,71 @@ int wgcs_recv_source_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgcs_aea
 int wgcs_route_dst_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const uint64_t *d_off, uint64_t stride,
                          uint32_t offset, const int32_t *d_size, uint32_t n, const uint8_t *d_image,
                          size_t image_bytes, uint32_t *d_peer, void *stream);
+
+/* ---- per-keypair state: replay filter and send nonce (replay/replay.go,
+ * device/receive.go:414-420, device/send.go:383-390) ----
+ * The two steps of the per-packet path that are sequential per keypair.  Their
+ * state sits in device memory beside the AEAD key table and is indexed by its
+ * rows: one wgcs_replay_filter and one uint64 send nonce per key.  The caller
+ * zeroes a row (a stream-ordered memset) when it overwrites the key. */
+
+#define WGCS_REJECT_AFTER_MESSAGES 0xFFFFFFFFFFFFDFFFull /* RejectAfterMessages, constants.go:14: the limit of both */
+
+/* replay.Filter: the highest value seen and a ring of 128 blocks of 64 bits
+ * (window 127 * 64 = 8,128).  All zero is the empty filter; Reset is a memset. */
+typedef struct wgcs_replay_filter {
+  uint64_t last;
+  uint64_t ring[128];
+} wgcs_replay_filter; /* 1,032 B, 8-byte aligned */
+
+/* Filter.Validate / Filter.Reset on a filter in host memory (no context, no
+ * device): 1 = accepted, 0 = rejected, WGCS_ERR_INVALID_ARG for NULL. */
+int wgcs_replay_validate(wgcs_replay_filter *f, uint64_t value, uint64_t limit);
+void wgcs_replay_reset(wgcs_replay_filter *f);
+
+/* The workspace of the two batch entry points below for n rows (or jobs): an
+ * upper bound, n <= 2^24.  d_work is the caller's device memory, 16-byte
+ * aligned; nothing is allocated inside an enqueue. */
+size_t wgcs_keyorder_work_bytes(uint32_t n);
+
+/* keypair.replayFilter.Validate over what wgcs_aead_open_batch left, a few
+ * ordinary launches, asynchronous on stream.  Row i takes part if
+ * d_pkts[i].key < n_keys and d_pkt_len[i] >= 0 or == WGCS_ERR_PACKET_TOO_SHORT
+ * (every message Open decrypted: receive.go:414-420 precedes the trim).  The
+ * rows of one key are validated against d_filters[key] in slot order:
+ * d_verdict[i] = d_pkt_len[i] if accepted, else WGCS_ERR_REPLAY.  Every other
+ * row gets d_verdict[i] = d_pkt_len[i] and touches no filter; filters of keys
+ * without a row are not written.  Afterwards each filter is, in all its bytes,
+ * what sequential Validate calls leave.  d_verdict may alias d_pkt_len and
+ * feeds wgcs_recv_source_batch.  n <= 2^24, n_keys <= 2^24; n == 0 is a no-op;
+ * WGCS_ERR_INVALID_ARG (nothing written) for a workspace that is too small. */
+int wgcs_replay_batch(wgcs_ctx *ctx, const wgcs_aead_pkt *d_pkts, const int32_t *d_pkt_len,
+                      const uint64_t *d_counter, uint32_t n, wgcs_replay_filter *d_filters, uint32_t n_keys,
+                      uint64_t limit, int32_t *d_verdict, void *d_work, size_t work_bytes, void *stream);
+
+/* The step between wgcs_route_dst_batch and wgcs_aead_seal_batch (send.go:
+ * 383-390): key and nonces of every Tun.Read job, from the outputs of
+ * wgcs_gso_split_batch (d_sizes, d_count, d_status; max_segs slots per job)
+ * and the peers of its slots.  d_peer_keys (wgcs_session_table_build rows,
+ * n_slots a power of two) maps a peer id to its key row.  Job j is kept iff
+ * d_status[j] == 0, 1 <= d_count[j] <= max_segs, d_peer[j * max_segs] is a
+ * peer found there with a key row < n_keys, and its nonces fit: the kept jobs
+ * of a key, in job order, take consecutive nonces from d_send_nonce[key], and
+ * a job fits iff its last nonce + 1 <= limit; after one that does not, no
+ * later job of that key is kept and d_send_nonce[key] = limit (send.go:386),
+ * else it advances by the counts of the kept jobs.
+ *   kept job     d_nbufs[j] = d_count[j], d_job_key[j] = key, and row
+ *                q = j * max_segs + k, k < d_count[j], of d_pkts is
+ *                {q * stride, nonce, (uint32_t)d_sizes[q], key}
+ *   dropped job  d_nbufs[j] = 0, d_job_key[j] = 0xFFFFFFFF
+ * and every other of the n_jobs * max_segs rows is {q * stride, 0, 0,
+ * 0xFFFFFFFF}, which wgcs_aead_seal_batch refuses untouched.  n_jobs <= 2^24,
+ * n_jobs * max_segs <= 2^28, n_keys <= 2^24; workspace as above for n_jobs. */
+int wgcs_send_assign_batch(wgcs_ctx *ctx, const int32_t *d_sizes, const uint32_t *d_peer, const int32_t *d_count,
+                           const int32_t *d_status, uint32_t n_jobs, uint32_t max_segs, uint64_t stride,
+                           const wgcs_session_slot *d_peer_keys, uint32_t n_slots, uint64_t *d_send_nonce,
+                           uint32_t n_keys, uint64_t limit, wgcs_aead_pkt *d_pkts, int32_t *d_nbufs,
+                           uint32_t *d_job_key, void *d_work, size_t work_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,7 @@ ERR_CMSG = -16
 ERR_SPLIT_OVERFLOW = -17
 ERR_AUTH = -18
 ERR_SOURCE = -19
+ERR_REPLAY = -20
 ERR_HIP = -100
 ERR_NOMEM = -101
 ERR_NO_DEVICE = -102
@@ -43,6 +44,7 @@ MODE_FOLD, MODE_L4_FILL, MODE_VALIDATE, MODE_PARTIAL, MODE_IP4HDR = 0, 1, 2, 3, 
 F_INPLACE = 0x1
 PKT_V6 = 0x01
 PEER_NONE = 0xFFFFFFFF  # Router.Find's nil
+REJECT_AFTER_MESSAGES = 0xFFFFFFFFFFFFDFFF  # constants.go:14
 
 
 class WgcsError(RuntimeError):
@@ -177,6 +179,12 @@ def load() -> C.CDLL:
         "wgcs_recv_classify_batch": ([vp, vp, vp, u64, vp, u32, vp, u32, vp, vp, vp], i32),
         "wgcs_recv_source_batch": ([vp, vp, vp, vp, vp, u32, u32, vp, sz, vp, vp, vp], i32),
         "wgcs_route_dst_batch": ([vp, vp, vp, u64, u32, vp, u32, vp, sz, vp, vp], i32),
+        "wgcs_replay_validate": ([vp, u64, u64], i32),
+        "wgcs_replay_reset": ([vp], None),
+        "wgcs_keyorder_work_bytes": ([u32], sz),
+        "wgcs_replay_batch": ([vp, vp, vp, vp, u32, vp, u32, u64, vp, vp, sz, vp], i32),
+        "wgcs_send_assign_batch": ([vp, vp, vp, vp, vp, u32, u32, u64, vp, u32, vp, u32, u64, vp, vp, vp, vp, sz, vp],
+                                   i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

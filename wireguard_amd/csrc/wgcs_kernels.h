@@ -64,4 +64,16 @@ hipError_t launch_route_dst(const uint8_t* arena, const uint64_t* off, uint64_t 
                             const int32_t* sizes, uint32_t n, const uint8_t* image, uint64_t image_bytes,
                             uint32_t* peer, hipStream_t s);
 
+// Per-keypair state (replay_kernels.hip) on a carved workspace (wgcs_keyorder.h):
+// the replay filter over open's counters, and key and nonces of every send job.
+struct KeyOrder;
+hipError_t launch_replay(const KeyOrder& ko, const wgcs_aead_pkt* pkts, const int32_t* pkt_len,
+                         const uint64_t* counter, uint32_t n, wgcs_replay_filter* filters, uint32_t n_keys,
+                         uint64_t limit, int32_t* verdict, hipStream_t s);
+hipError_t launch_send_assign(const KeyOrder& ko, const int32_t* sizes, const uint32_t* peer, const int32_t* count,
+                              const int32_t* status, uint32_t n_jobs, uint32_t max_segs, uint64_t stride,
+                              const wgcs_session_slot* peer_keys, uint32_t n_slots, uint64_t* send_nonce,
+                              uint32_t n_keys, uint64_t limit, wgcs_aead_pkt* pkts, int32_t* nbufs, uint32_t* job_key,
+                              hipStream_t s);
+
 }  // namespace wgcs
