@@ -39,6 +39,10 @@
  *   wgcs_recv_classify_batch  the loop body of RoutineReceiveFromPeers   device/receive.go:145-207
  *   wgcs_recv_source_batch    the allowed-source check            device/receive.go:438-482
  *   wgcs_route_dst_batch      the routing step of RoutineReadFromTUN     device/send.go:264-293
+ *   wgcs_replay_batch         keypair.replayFilter.Validate       device/receive.go:414-420
+ *   wgcs_send_assign_batch    keypair.sendNonce and its limit     device/send.go:383-390
+ *   wgcs_write_build_batch    one Tun.Write per receive batch and peer, with the peer's
+ *                             bookkeeping (_host: on host arrays) device/receive.go:178-228, :398-504
  *   wgcs_stager_*             Tun.Read batch staging              tun/tun.go:477-508
  *   wgcs_wstager_*            Tun.Write batch staging             tun/tun.go:654-700
  * Status codes map 1:1 onto the reference's Go errors (see WGCS_ERR_*).
@@ -70,7 +74,8 @@ extern "C" {
 #define WGCS_ERR_CSUM_OFFSET (-11)      /* "end of checksum offset (%d) exceeds packet length (%d)" tun.go:625 */
 #define WGCS_ERR_READ_OVERFLOW (-12)    /* "read length %d overflows bufs element length %d" tun.go:546 */
 #define WGCS_ERR_OUT_OF_RANGE (-13)     /* input on which the Go code would panic (slice bounds) */
-#define WGCS_ERR_BATCH_FULL (-14)       /* stager: the open batch has no room; submit it first */
+#define WGCS_ERR_BATCH_FULL (-14)       /* stager: the open batch has no room; submit it first.
+                                           wgcs_write_build_batch: a batch has more peers than calls_per_batch */
 #define WGCS_ERR_NOT_READY (-15)        /* stager: batch id not submitted / recycled */
 #define WGCS_ERR_CMSG (-16)             /* "error parsing socket control message: %w" conn/gso.go:45 */
 #define WGCS_ERR_SPLIT_OVERFLOW (-17)   /* "splitting coalesced packet resulted in overflow" conn/bind.go:565 */
@@ -325,6 +330,10 @@ int wgcs_ring_handle_virtio_read_cap(wgcs_ring *ring, uint8_t *read_buf, size_t 
  * and toWrite in d_to_write[first : first + d_n_write[c]].  Every byte that
  * Tun.Write hands to write(2) -- bufs[i][offset-10:len] for i in toWrite --
  * equals the reference's, and so does every other byte of every slice.
+ * A call with n == 0 is a no-op: d_status[c] = 0, d_n_write[c] = 0, and nothing
+ * else is read or written -- not d_bufs, not d_to_write, not the arena.  The
+ * fixed layout of wgcs_write_build_batch relies on it: its unused call rows
+ * and the calls of peers without a packet to write are such calls.
  * One workgroup per call, async on stream. */
 typedef struct wgcs_gro_buf {
   uint64_t off; /* slice start in the arena */
@@ -759,6 +768,75 @@ int wgcs_send_assign_batch(wgcs_ctx *ctx, const int32_t *d_sizes, const uint32_t
                            const wgcs_session_slot *d_peer_keys, uint32_t n_slots, uint64_t *d_send_nonce,
                            uint32_t n_keys, uint64_t limit, wgcs_aead_pkt *d_pkts, int32_t *d_nbufs,
                            uint32_t *d_job_key, void *d_work, size_t work_bytes, void *stream);
+
+/* ---- the Write calls of the receive chain, one per batch and peer
+ * (device/receive.go:178-228, :398-504) ----
+ * RoutineReceiveIncoming sorts the items of a recvmmsg batch into one
+ * container per peer; each peer's RoutineSendToInternet validates its
+ * container in slot order, keeps the peer's books for every message that
+ * passes the replay filter (rxBytes, validTailPacket, dataPacketReceived,
+ * :407-436, :485-494) and hands the packets that are left to one Tun.Write
+ * (:483-504).  This step builds those calls, and one accounting row beside
+ * each, from what wgcs_recv_source_batch left, so that wgcs_handle_gro_batch
+ * can follow on the same stream with no host step between them.
+ *
+ * Batch b owns rows q in [b * n_msgs, (b + 1) * n_msgs) of d_pkts / d_verdict.
+ * Row q is validated iff d_pkts[q].key < n_keys, d_key_peer[key] !=
+ * WGCS_PEER_NONE and d_verdict[q] is >= 0, WGCS_ERR_SOURCE or
+ * WGCS_ERR_PACKET_TOO_SHORT: the messages that passed replayFilter.Validate
+ * (wgcs_replay_batch's participation rule minus its rejects).  It is kept iff
+ * it is validated and d_verdict[q] > 0.  Every other row takes no part.
+ *
+ * The groups of a batch are the distinct peers d_key_peer[key] of its
+ * validated rows, ordered by each peer's first validated row (Go leaves the
+ * order open: map iteration, one goroutine per peer); the previous and the
+ * current keypair of one peer share a group.  Group g of batch b has row
+ * c = b * calls_per_batch + g of d_calls and d_groups:
+ *   d_calls[c]  = {first, n, offset, gro_flags}: n = the group's kept rows,
+ *                 first = b * n_msgs + the kept rows of the groups before it
+ *   d_bufs[first + k] = {d_pkts[q].off, offset + d_verdict[q], cap} for the
+ *                 group's k-th kept row q in slot order (receive.go:483)
+ *   d_groups[c] as below; n == 0 for a peer of keepalives or rejected sources only
+ * d_n_groups[b] = the number of groups, d_status[b] = 0.  Every other row the
+ * batch owns is written too: unused call rows are {b * n_msgs, 0, offset,
+ * gro_flags}, unused group rows {WGCS_PEER_NONE, -1, 0, 0, 0}, and the rows of
+ * d_bufs past the batch's kept rows are all zero.  So wgcs_handle_gro_batch
+ * runs over all n_batches * calls_per_batch call rows (n == 0 is a no-op
+ * there), and afterwards the host reads, per call row, d_groups and GRO's
+ * d_status / d_n_write / d_to_write.
+ *
+ * A refused batch builds nothing: every one of its call and group rows is the
+ * unused one and its d_bufs rows are zero; d_n_groups[b] is still the count.
+ * d_status[b] = WGCS_ERR_OUT_OF_RANGE if some kept row has offset + verdict >
+ * cap (Go would panic slicing), else WGCS_ERR_BATCH_FULL if the batch has more
+ * groups than calls_per_batch.
+ *
+ * One ordinary launch, asynchronous on stream; no workspace, no atomics, the
+ * same bytes every time.  The inputs are only read.  WGCS_ERR_INVALID_ARG, and
+ * nothing written, unless 1 <= calls_per_batch <= n_msgs <= WGCS_GRO_MAX_CALL,
+ * n_batches * n_msgs <= 2^28, 0 <= offset <= cap, no pointer is NULL, d_pkts /
+ * d_bufs / d_calls are 16-byte aligned, d_groups 8-byte and the 32-bit arrays
+ * 4-byte aligned.  n_batches == 0 is a no-op.
+ * wgcs_write_build_host is the same rule on host arrays (no context, no
+ * device), array for array. */
+#define WGCS_GROUP_DATA 0x1u /* dataPacketReceived, receive.go:436 */
+typedef struct wgcs_write_group {
+  uint32_t peer;     /* d_key_peer[key] of the group's rows; WGCS_PEER_NONE: unused row */
+  int32_t tail;      /* validTailPacket as a row index q of the whole table; -1: unused row */
+  uint32_t flags;    /* WGCS_GROUP_DATA: some validated row has d_pkts[q].len > 32 */
+  uint32_t n_valid;  /* rows of this peer that passed the replay filter */
+  uint64_t rx_bytes; /* sum of d_pkts[q].len over them (= len(item.packet) + MinMessageSize, :431) */
+} wgcs_write_group;  /* 24 B, 8-byte aligned */
+
+int wgcs_write_build_batch(wgcs_ctx *ctx, const wgcs_aead_pkt *d_pkts, const int32_t *d_verdict,
+                           uint32_t n_msgs, uint32_t n_batches, const uint32_t *d_key_peer, uint32_t n_keys,
+                           int32_t offset, uint32_t cap, uint32_t gro_flags, uint32_t calls_per_batch,
+                           wgcs_gro_buf *d_bufs, wgcs_gro_call *d_calls, wgcs_write_group *d_groups,
+                           int32_t *d_n_groups, int32_t *d_status, void *stream);
+int wgcs_write_build_host(const wgcs_aead_pkt *pkts, const int32_t *verdict, uint32_t n_msgs, uint32_t n_batches,
+                          const uint32_t *key_peer, uint32_t n_keys, int32_t offset, uint32_t cap,
+                          uint32_t gro_flags, uint32_t calls_per_batch, wgcs_gro_buf *bufs, wgcs_gro_call *calls,
+                          wgcs_write_group *groups, int32_t *n_groups, int32_t *status);
 
 #ifdef __cplusplus
 }

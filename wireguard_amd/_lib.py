@@ -45,6 +45,7 @@ F_INPLACE = 0x1
 PKT_V6 = 0x01
 PEER_NONE = 0xFFFFFFFF  # Router.Find's nil
 REJECT_AFTER_MESSAGES = 0xFFFFFFFFFFFFDFFF  # constants.go:14
+GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
 
 
 class WgcsError(RuntimeError):
@@ -185,6 +186,8 @@ def load() -> C.CDLL:
         "wgcs_replay_batch": ([vp, vp, vp, vp, u32, vp, u32, u64, vp, vp, sz, vp], i32),
         "wgcs_send_assign_batch": ([vp, vp, vp, vp, vp, u32, u32, u64, vp, u32, vp, u32, u64, vp, vp, vp, vp, sz, vp],
                                    i32),
+        "wgcs_write_build_batch": ([vp, vp, vp, u32, u32, vp, u32, i32, u32, u32, u32, vp, vp, vp, vp, vp, vp], i32),
+        "wgcs_write_build_host": ([vp, vp, u32, u32, vp, u32, i32, u32, u32, u32, vp, vp, vp, vp, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

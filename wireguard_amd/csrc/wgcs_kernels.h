@@ -76,4 +76,11 @@ hipError_t launch_send_assign(const KeyOrder& ko, const int32_t* sizes, const ui
                               uint32_t n_keys, uint64_t limit, wgcs_aead_pkt* pkts, int32_t* nbufs, uint32_t* job_key,
                               hipStream_t s);
 
+// The Write calls of every receive batch, one per peer (write_kernels.hip, the
+// wave form of wgcs_write_plan.h): one wave per batch, one launch.
+hipError_t launch_write_build(const wgcs_aead_pkt* pkts, const int32_t* verdict, uint32_t n_msgs, uint32_t n_batches,
+                              const uint32_t* key_peer, uint32_t n_keys, int32_t offset, uint32_t cap,
+                              uint32_t gro_flags, uint32_t calls_per_batch, wgcs_gro_buf* bufs, wgcs_gro_call* calls,
+                              wgcs_write_group* groups, int32_t* n_groups, int32_t* status, hipStream_t s);
+
 }  // namespace wgcs
