@@ -41,6 +41,9 @@
  *   wgcs_route_dst_batch      the routing step of RoutineReadFromTUN     device/send.go:264-293
  *   wgcs_replay_batch         keypair.replayFilter.Validate       device/receive.go:414-420
  *   wgcs_send_assign_batch    keypair.sendNonce and its limit     device/send.go:383-390
+ *   wgcs_cookie_*             CookieChecker / CookieGenerator      device/cookie.go
+ *   wgcs_handshake_screen_batch  CheckMAC1, CheckMAC2 and the cookie reply at the top of
+ *                             RoutineHandshake                     device/receive.go:270-287
  *   wgcs_write_build_batch    one Tun.Write per receive batch and peer, with the peer's
  *                             bookkeeping (_host: on host arrays) device/receive.go:178-228, :398-504
  *   wgcs_stager_*             Tun.Read batch staging              tun/tun.go:477-508
@@ -82,6 +85,7 @@ extern "C" {
 #define WGCS_ERR_AUTH (-18)             /* "chacha20poly1305: message authentication failed" receive.go:380 */
 #define WGCS_ERR_SOURCE (-19)           /* "packet with disallowed source address" receive.go:452-457, :472-477 */
 #define WGCS_ERR_REPLAY (-20)           /* replayFilter.Validate said no: the packet is dropped  receive.go:418-420 */
+#define WGCS_ERR_MAC1 (-21)             /* "Received packet with invalid mac1" receive.go:272-275 */
 #define WGCS_ERR_HIP (-100)           /* HIP runtime error (message: wgcs_last_error) */
 #define WGCS_ERR_NOMEM (-101)
 #define WGCS_ERR_NO_DEVICE (-102)
@@ -837,6 +841,97 @@ int wgcs_write_build_host(const wgcs_aead_pkt *pkts, const int32_t *verdict, uin
                           const uint32_t *key_peer, uint32_t n_keys, int32_t offset, uint32_t cap,
                           uint32_t gro_flags, uint32_t calls_per_batch, wgcs_gro_buf *bufs, wgcs_gro_call *calls,
                           wgcs_write_group *groups, int32_t *n_groups, int32_t *status);
+
+/* ---- the handshake screen: MAC1, MAC2 and cookie replies (device/cookie.go,
+ * device/receive.go:270-287, device/send.go:176-187) ----
+ * The denial-of-service defence in front of the Noise handshake.  Every
+ * initiation and response carries MAC1 = BLAKE2s-128(mac1_key, msg[0 : len-32])
+ * at [len-32, len-16) and MAC2 at [len-16, len).  A message with a wrong MAC1
+ * is dropped.  Under load the receiver also wants MAC2 =
+ * BLAKE2s-128(cookie, msg[0 : len-16]) with cookie = BLAKE2s-128(secret, source
+ * address), and answers a message without it by a cookie reply: the cookie
+ * sealed with XChaCha20-Poly1305 under cookie_key, with the message's MAC1 as
+ * additional data.  All of it is stateless and per message.
+ *
+ * Clock and randomness stay with the caller.  The reference compares
+ * secretSetAt with CookieRefreshTime (120 s) inside CheckMAC2 and CreateReply
+ * (cookie.go:156, :192-203); here the caller draws a new `secret` before it
+ * checks a message or enqueues a batch whenever the one it holds is that old.
+ * Verdicts and replies are then the reference's: a MAC2 made from a cookie of
+ * the old secret fails against the new one, and CreateReply would have
+ * refreshed before sealing anyway.  The 24 random nonce bytes of every reply
+ * (cookie.go:231) are the caller's as well; nothing here draws randomness or
+ * reads a clock.  What comes after a pass -- the rate limiter, the Noise
+ * handshake -- and IsUnderLoad's rule are the host's. */
+typedef struct wgcs_cookie_checker { /* 96 B; 4-byte aligned on the device */
+  uint8_t mac1_key[32];              /* BLAKE2s-256("mac1----" | pub)   cookie.go:106-109 */
+  uint8_t cookie_key[32];            /* BLAKE2s-256("cookie--" | pub)   :112-114 */
+  uint8_t secret[32];                /* mac2.secret, the caller's random bytes */
+} wgcs_cookie_checker;
+typedef struct wgcs_src_addr { /* 20 B: Endpoint.DstToBytes() */
+  uint8_t b[18];               /* IP bytes (4 or 16) then LE16 port: netip.AddrPort.MarshalBinary */
+  uint8_t len;                 /* 6 or 18 */
+  uint8_t pad;
+} wgcs_src_addr;
+
+#define WGCS_HS_NONE 0   /* not an initiation or a response: not this step's row */
+#define WGCS_HS_PASS 1   /* MAC1 holds, and under load MAC2 too: on to the rate limiter and Noise */
+#define WGCS_HS_COOKIE 2 /* under load without a valid MAC2: send the row's cookie reply */
+
+/* Host functions, no context and no device.  msg is a handshake message of len
+ * bytes; WGCS_ERR_OUT_OF_RANGE for len < 32 (Go would panic slicing) or
+ * len > 65535, WGCS_ERR_INVALID_ARG for a NULL pointer or a source whose len is
+ * neither 6 nor 18.
+ * CookieChecker.Init and CookieGenerator.Init (cookie.go:102-115, :269-282):
+ * both keys from the static public key; secret is zeroed. */
+int wgcs_cookie_checker_init(wgcs_cookie_checker *ck, const uint8_t pub[32]);
+/* CheckMAC1 (:121-146) and CheckMAC2 (:153-176): 1 or 0.  Tags are compared
+ * over all 16 bytes, as hmac.Equal does. */
+int wgcs_cookie_check_mac1(const wgcs_cookie_checker *ck, const uint8_t *msg, size_t len);
+int wgcs_cookie_check_mac2(const wgcs_cookie_checker *ck, const uint8_t *msg, size_t len, const wgcs_src_addr *src);
+/* CreateReply (:184-243) with SendHandshakeCookie's receiver = msg[4:8]
+ * (send.go:176-187): the 64-byte MessageCookieReply LE32 3 | LE32 receiver |
+ * nonce | sealed cookie. */
+int wgcs_cookie_create_reply(const wgcs_cookie_checker *ck, const uint8_t *msg, size_t len, const wgcs_src_addr *src,
+                             const uint8_t nonce[24], uint8_t out[64]);
+/* AddMACs (:287-314), the sender's side: writes MAC1, copies it to last_mac1
+ * (optional), and with a cookie (16 bytes: the caller holds one that is not
+ * older than 120 s) writes MAC2; with NULL the MAC2 field is left as it is. */
+int wgcs_cookie_add_macs(const uint8_t mac1_key[32], const uint8_t *cookie, uint8_t *msg, size_t len,
+                         uint8_t *last_mac1);
+/* ConsumeReply (:319-339): 1 and the cookie when the reply opens under
+ * cookie_key with last_mac1 as additional data, else 0 (cookie untouched). */
+int wgcs_cookie_consume_reply(const uint8_t cookie_key[32], const uint8_t last_mac1[16], const uint8_t reply[64],
+                              uint8_t cookie[16]);
+
+/* The screen over the rows that wgcs_recv_classify_batch wrote: an ordinary
+ * launch, asynchronous on stream (NULL: the context's), n <= 2^28, n == 0 a
+ * no-op.  It reads the arena and never writes it; messages sit at any byte
+ * offset, and the arena is read in the aligned 4-byte words that hold a message,
+ * so with a 4-byte aligned d_arena it must be readable from align_down(off, 4)
+ * through align_up(off + len, 4) (inside the contract of the other batch entry
+ * points above).  Row q:
+ *   d_type[q] other than 1 or 2   d_verdict[q] = WGCS_HS_NONE, nothing else read
+ *                                 (transport rows, cookie replies -- ConsumeReply
+ *                                 takes a per-peer lock and stays with the host --
+ *                                 unknown and negative types)
+ *   d_pkts[q].len != 148 (type 1) / 92 (type 2)   WGCS_ERR_INVALID_ARG, nothing read
+ *   MAC1 of the message at d_pkts[q].off is wrong WGCS_ERR_MAC1
+ *   under_load == 0                               WGCS_HS_PASS; MAC2 is not looked at
+ *   under_load != 0, with the cookie of d_src[q]:
+ *     d_src[q].len neither 6 nor 18               WGCS_ERR_INVALID_ARG
+ *     MAC2 matches                                WGCS_HS_PASS
+ *     else                                        WGCS_HS_COOKIE, and the 64 bytes at
+ *                                                 d_reply + 64 * q are the reply of
+ *                                                 wgcs_cookie_create_reply with the
+ *                                                 nonce d_nonce[24 * q : 24 * q + 24]
+ * The d_reply rows of every other verdict keep what they held.  d_src, d_nonce
+ * and d_reply may be NULL when under_load == 0.  d_pkts is 8-byte aligned;
+ * d_type, d_checker, d_src, d_nonce, d_verdict and d_reply are 4-byte aligned. */
+int wgcs_handshake_screen_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgcs_aead_pkt *d_pkts,
+                                const int32_t *d_type, uint32_t n, const wgcs_cookie_checker *d_checker,
+                                const wgcs_src_addr *d_src, uint32_t under_load, const uint8_t *d_nonce,
+                                int32_t *d_verdict, uint8_t *d_reply, void *stream);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,7 @@ ERR_SPLIT_OVERFLOW = -17
 ERR_AUTH = -18
 ERR_SOURCE = -19
 ERR_REPLAY = -20
+ERR_MAC1 = -21
 ERR_HIP = -100
 ERR_NOMEM = -101
 ERR_NO_DEVICE = -102
@@ -45,6 +46,7 @@ F_INPLACE = 0x1
 PKT_V6 = 0x01
 PEER_NONE = 0xFFFFFFFF  # Router.Find's nil
 REJECT_AFTER_MESSAGES = 0xFFFFFFFFFFFFDFFF  # constants.go:14
+HS_NONE, HS_PASS, HS_COOKIE = 0, 1, 2  # wgcs_handshake_screen_batch's verdicts
 GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
 
 
@@ -188,6 +190,13 @@ def load() -> C.CDLL:
                                    i32),
         "wgcs_write_build_batch": ([vp, vp, vp, u32, u32, vp, u32, i32, u32, u32, u32, vp, vp, vp, vp, vp, vp], i32),
         "wgcs_write_build_host": ([vp, vp, u32, u32, vp, u32, i32, u32, u32, u32, vp, vp, vp, vp, vp], i32),
+        "wgcs_cookie_checker_init": ([vp, vp], i32),
+        "wgcs_cookie_check_mac1": ([vp, vp, sz], i32),
+        "wgcs_cookie_check_mac2": ([vp, vp, sz, vp], i32),
+        "wgcs_cookie_create_reply": ([vp, vp, sz, vp, vp, vp], i32),
+        "wgcs_cookie_add_macs": ([vp, vp, vp, sz, vp], i32),
+        "wgcs_cookie_consume_reply": ([vp, vp, vp, vp], i32),
+        "wgcs_handshake_screen_batch": ([vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

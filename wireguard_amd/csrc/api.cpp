@@ -247,6 +247,7 @@ const char* wgcs_strerror(int status) {
     case WGCS_ERR_AUTH: return "chacha20poly1305: message authentication failed";
     case WGCS_ERR_SOURCE: return "packet with disallowed source address";
     case WGCS_ERR_REPLAY: return "replayed or out-of-window counter";
+    case WGCS_ERR_MAC1: return "received packet with invalid mac1";
     case WGCS_ERR_HIP: return "HIP runtime error";
     case WGCS_ERR_NOMEM: return "out of memory";
     case WGCS_ERR_NO_DEVICE: return "no HIP device";

@@ -83,4 +83,10 @@ hipError_t launch_write_build(const wgcs_aead_pkt* pkts, const int32_t* verdict,
                               uint32_t gro_flags, uint32_t calls_per_batch, wgcs_gro_buf* bufs, wgcs_gro_call* calls,
                               wgcs_write_group* groups, int32_t* n_groups, int32_t* status, hipStream_t s);
 
+// The handshake screen (cookie_kernels.hip): MAC1, and under load MAC2 and the
+// cookie reply, for the rows that classify typed 1 or 2.
+hipError_t launch_hs_screen(const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* types, uint32_t n,
+                            const wgcs_cookie_checker* checker, const wgcs_src_addr* srcs, uint32_t under_load,
+                            const uint8_t* nonces, int32_t* verdict, uint8_t* replies, hipStream_t s);
+
 }  // namespace wgcs
