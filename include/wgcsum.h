@@ -44,6 +44,11 @@
  *   wgcs_cookie_*             CookieChecker / CookieGenerator      device/cookie.go
  *   wgcs_handshake_screen_batch  CheckMAC1, CheckMAC2 and the cookie reply at the top of
  *                             RoutineHandshake                     device/receive.go:270-287
+ *   wgcs_x25519 / _batch      curve25519.X25519                    device/noise_helpers.go:93-105
+ *   wgcs_noise_* / wgcs_peer_keys_*  the stateless part of the Noise handshake's first message
+ *                                                                  device/noise.go:344-457
+ *   wgcs_handshake_consume_batch  ConsumeMessageInitiation up to its replay / flood check
+ *                                                                  device/noise.go:405-457
  *   wgcs_write_build_batch    one Tun.Write per receive batch and peer, with the peer's
  *                             bookkeeping (_host: on host arrays) device/receive.go:178-228, :398-504
  *   wgcs_stager_*             Tun.Read batch staging              tun/tun.go:477-508
@@ -86,6 +91,8 @@ extern "C" {
 #define WGCS_ERR_SOURCE (-19)           /* "packet with disallowed source address" receive.go:452-457, :472-477 */
 #define WGCS_ERR_REPLAY (-20)           /* replayFilter.Validate said no: the packet is dropped  receive.go:418-420 */
 #define WGCS_ERR_MAC1 (-21)             /* "Received packet with invalid mac1" receive.go:272-275 */
+#define WGCS_ERR_LOW_ORDER (-22)        /* "bad input point: low order point" curve25519.X25519, noise.go:421-424 */
+#define WGCS_ERR_NO_PEER (-23)          /* GetPeer found none, or it is not running / has no shared secret  noise.go:432-443 */
 #define WGCS_ERR_HIP (-100)           /* HIP runtime error (message: wgcs_last_error) */
 #define WGCS_ERR_NOMEM (-101)
 #define WGCS_ERR_NO_DEVICE (-102)
@@ -932,6 +939,111 @@ int wgcs_handshake_screen_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgc
                                 const int32_t *d_type, uint32_t n, const wgcs_cookie_checker *d_checker,
                                 const wgcs_src_addr *d_src, uint32_t under_load, const uint8_t *d_nonce,
                                 int32_t *d_verdict, uint8_t *d_reply, void *stream);
+
+/* ---- X25519 and the consumption of handshake initiations (device/noise.go,
+ * device/noise_helpers.go) ----
+ * Every initiation that passes the screen costs ConsumeMessageInitiation
+ * (noise.go:405-492) one Curve25519 scalar multiplication, 37 BLAKE2s
+ * compressions, two ChaCha20-Poly1305 opens and a peer lookup by public key.
+ * Everything up to the replay / flood check (:458) is stateless and per
+ * message -- no clock, no randomness, no per-peer lock -- and runs here over
+ * the batch where it landed.  The rest stays with the host: the comparison
+ * with lastTimestamp, the HandshakeInitationRate rule and the handshake-state
+ * update (:458-491), for which a row of wgcs_hs_init holds what they need;
+ * and CreateMessageResponse / ConsumeMessageResponse, which go through a
+ * per-handshake ephemeral private key.  Nothing here draws randomness or reads
+ * a clock. */
+
+/* curve25519.X25519 (RFC 7748 section 5; noise_helpers.go:93-105): the scalar is
+ * clamped inside, bit 255 of the point is ignored, a u in [p, 2^255) is
+ * reduced, out is fully reduced.  0, or WGCS_ERR_LOW_ORDER with out zeroed for
+ * an all-zero result; INVALID_ARG for a NULL pointer.  Host, no device. */
+int wgcs_x25519(uint8_t out[32], const uint8_t scalar[32], const uint8_t point[32]);
+
+typedef struct wgcs_noise_responder { /* 96 B, 4-byte aligned on the device */
+  uint8_t private_key[32];            /* d.keys.privateKey */
+  uint8_t hash0[32];                  /* mixHash(InitialHash, public key)   noise.go:415 */
+  uint8_t chain0[32];                 /* InitialChainKey                    noise.go:92 */
+} wgcs_noise_responder;
+/* Fills r for the static private key; public_key (optional) receives
+ * privateKey.publicKey().  INVALID_ARG for a NULL r or private_key. */
+int wgcs_noise_responder_init(wgcs_noise_responder *r, const uint8_t private_key[32], uint8_t public_key[32]);
+
+typedef struct wgcs_peer_key { /* 72 B: one row of the table GetPeer reads */
+  uint8_t public_key[32];
+  uint8_t shared[32]; /* precomputedSharedSecret = X25519(private, public_key) (noise.go:305); zero if that
+                         is low order */
+  uint32_t peer;      /* caller's peer id, never WGCS_PEER_NONE */
+  uint32_t flags;     /* bit 0: peer.isRunning */
+} wgcs_peer_key;
+#define WGCS_PEER_RUNNING 0x1u
+/* The table of n peers: rows sorted by public_key (memcmp order), each with its
+ * shared secret under r's private key.  flags may be NULL (every peer
+ * running).  INVALID_ARG for a duplicate key, peer == WGCS_PEER_NONE or a NULL
+ * argument with n > 0; n == 0 writes nothing. */
+int wgcs_peer_keys_build(const wgcs_noise_responder *r, const uint8_t *public_keys /* 32 * n */,
+                         const uint32_t *peers, const uint32_t *flags, uint32_t n, wgcs_peer_key *table);
+/* the row of public_key, or -1 (also for a NULL argument) */
+int wgcs_peer_keys_find(const wgcs_peer_key *table, uint32_t n, const uint8_t public_key[32]);
+
+typedef struct wgcs_hs_init { /* 128 B: what the host needs for noise.go:458-491 */
+  uint32_t peer;              /* the table row's peer, WGCS_PEER_NONE until one is found */
+  uint32_t sender;            /* LE32 msg[4:8]: hs.remoteIndex */
+  uint8_t timestamp[12];      /* the decrypted tai64n timestamp */
+  uint8_t pad[12];
+  uint8_t hash[32];           /* after mixHash(msg.Timestamp) */
+  uint8_t chain_key[32];      /* after the second KDF2 */
+  uint8_t ephemeral[32];      /* msg[8:40]: hs.remoteEphemeral */
+} wgcs_hs_init;
+
+#define WGCS_HS_CONSUMED 3 /* the initiation is authentic: on to the timestamp and flood rules */
+
+/* The whole stateless part (noise.go:405-457) for one message, on the host: the
+ * verdict of wgcs_handshake_consume_batch below for a row of type 1 that
+ * passed the screen, with *out filled as that row's d_out.  len != 148 or a
+ * NULL pointer (table may be NULL when n_peers == 0): WGCS_ERR_INVALID_ARG. */
+int wgcs_noise_consume_initiation(const wgcs_noise_responder *r, const wgcs_peer_key *table, uint32_t n_peers,
+                                  const uint8_t *msg, size_t len, wgcs_hs_init *out);
+/* The sender's side, CreateMessageInitiation (noise.go:344-403), with the
+ * caller's ephemeral private key, timestamp and sender index: the 148 bytes
+ * with zero MACs (wgcs_cookie_add_macs fills them), and (optional) the
+ * handshake's hash and chaining key after it.  WGCS_ERR_LOW_ORDER where a
+ * shared secret is zero (:366-369, :381-383; msg is then zeroed). */
+int wgcs_noise_create_initiation(const uint8_t static_private[32], const uint8_t remote_static[32],
+                                 const uint8_t ephemeral_private[32], const uint8_t timestamp[12], uint32_t sender,
+                                 uint8_t msg[148], uint8_t hash[32], uint8_t chain_key[32]);
+
+/* n scalar multiplications on the device, row q of d_scalars and d_points (32
+ * bytes each, 4-byte aligned) into row q of d_out, with d_status[q] = 0 or
+ * WGCS_ERR_LOW_ORDER (the row zeroed).  Asynchronous on stream (NULL: the
+ * context's); n <= 2^28, n == 0 a no-op. */
+int wgcs_x25519_batch(wgcs_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint32_t n, uint8_t *d_out,
+                      int32_t *d_status, void *stream);
+
+/* ConsumeMessageInitiation up to :457 over the rows the screen passed: an
+ * ordinary launch with the screen's contract (asynchronous on stream, n <=
+ * 2^28, n == 0 a no-op, the arena only read, in the aligned 4-byte words that
+ * hold a message).  d_gate is the screen's d_verdict -- the host's rate limiter
+ * masks rows in it between the two launches when under load -- or NULL, which
+ * selects every row of type 1; d_verdict must not be d_gate.  Row q:
+ *   d_type[q] != 1 or d_gate[q] != WGCS_HS_PASS   d_verdict[q] = WGCS_HS_NONE; d_out[q] untouched,
+ *                                                 nothing else read
+ *   d_pkts[q].len != 148 or LE32 msg[0:4] != 1    WGCS_ERR_INVALID_ARG; d_out[q] untouched   noise.go:406
+ *   X25519(private, msg[8:40]) is all zero        WGCS_ERR_LOW_ORDER                          :421-424
+ *   msg[40:88] does not open                      WGCS_ERR_AUTH, peer WGCS_PEER_NONE          :427-430
+ *   the opened key is not in d_table, its row is
+ *   not running or its shared is all zero         WGCS_ERR_NO_PEER                            :432-443
+ *   msg[88:116] does not open                     WGCS_ERR_AUTH, peer the row's               :451-455
+ *   otherwise                                     WGCS_HS_CONSUMED, the whole d_out[q]
+ * For the four failures d_out[q] is zero but for sender and peer (the found
+ * row's id, else WGCS_PEER_NONE): no key material is written for a row that
+ * failed.  d_responder and d_table are device memory (d_table may be NULL when
+ * n_peers == 0); d_pkts is 8-byte aligned, everything else 4-byte aligned.
+ * The static private key lives in device memory for as long as d_responder does. */
+int wgcs_handshake_consume_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgcs_aead_pkt *d_pkts,
+                                 const int32_t *d_type, const int32_t *d_gate, uint32_t n,
+                                 const wgcs_noise_responder *d_responder, const wgcs_peer_key *d_table,
+                                 uint32_t n_peers, int32_t *d_verdict, wgcs_hs_init *d_out, void *stream);
 
 #ifdef __cplusplus
 }

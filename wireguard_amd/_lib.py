@@ -37,6 +37,8 @@ ERR_AUTH = -18
 ERR_SOURCE = -19
 ERR_REPLAY = -20
 ERR_MAC1 = -21
+ERR_LOW_ORDER = -22
+ERR_NO_PEER = -23
 ERR_HIP = -100
 ERR_NOMEM = -101
 ERR_NO_DEVICE = -102
@@ -47,6 +49,8 @@ PKT_V6 = 0x01
 PEER_NONE = 0xFFFFFFFF  # Router.Find's nil
 REJECT_AFTER_MESSAGES = 0xFFFFFFFFFFFFDFFF  # constants.go:14
 HS_NONE, HS_PASS, HS_COOKIE = 0, 1, 2  # wgcs_handshake_screen_batch's verdicts
+HS_CONSUMED = 3  # wgcs_handshake_consume_batch's
+PEER_RUNNING = 0x1  # wgcs_peer_key.flags: peer.isRunning
 GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
 
 
@@ -197,6 +201,14 @@ def load() -> C.CDLL:
         "wgcs_cookie_add_macs": ([vp, vp, vp, sz, vp], i32),
         "wgcs_cookie_consume_reply": ([vp, vp, vp, vp], i32),
         "wgcs_handshake_screen_batch": ([vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp], i32),
+        "wgcs_x25519": ([vp, vp, vp], i32),
+        "wgcs_noise_responder_init": ([vp, vp, vp], i32),
+        "wgcs_peer_keys_build": ([vp, vp, vp, vp, u32, vp], i32),
+        "wgcs_peer_keys_find": ([vp, u32, vp], i32),
+        "wgcs_noise_consume_initiation": ([vp, vp, u32, vp, sz, vp], i32),
+        "wgcs_noise_create_initiation": ([vp, vp, vp, vp, u32, vp, vp, vp], i32),
+        "wgcs_x25519_batch": ([vp, vp, vp, u32, vp, vp, vp], i32),
+        "wgcs_handshake_consume_batch": ([vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

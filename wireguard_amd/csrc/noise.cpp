@@ -1,0 +1,166 @@
+// noise.cpp -- the host functions of the handshake consume step (include/wgcsum.h),
+// no context and no device:
+//   wgcs_x25519                      curve25519.X25519              device/noise_helpers.go:93-105
+//   wgcs_noise_responder_init        d.keys and the first mixHash   device/noise.go:91-94, :415
+//   wgcs_peer_keys_build / _find     GetPeer and precomputedSharedSecret   :305, :432
+//   wgcs_noise_consume_initiation    ConsumeMessageInitiation       :405-457
+//   wgcs_noise_create_initiation     CreateMessageInitiation        :344-403
+// They run the scalar code of wgcs_x25519.h and wgcs_noise.h, the code the
+// lanes of noise_kernels.hip run.  Plain C++: a host test program
+// (tests/noise_host/noise_host.cpp) links this file as it is.
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>  // the library's build compiles every file as HIP: WGCS_HD's qualifiers
+#endif
+
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/wgcsum.h"
+#include "wgcs_noise.h"
+
+using namespace wgcs;
+
+namespace {
+
+const char kNoiseConstruction[] = "Noise_IKpsk2_25519_ChaChaPoly_BLAKE2s";  // noise.go:43
+const char kWGIdentifier[] = "WireGuard v1 zx2c4 Jason@zx2c4.com";          // :44
+
+void words_of(const uint8_t* p, uint32_t n_words, uint32_t* w) {
+  for (uint32_t i = 0; i < n_words; ++i) w[i] = b2s_load_le32(p, 4 * i, 4 * n_words);
+}
+
+void bytes_of(const uint32_t* w, uint32_t n_words, uint8_t* p) {
+  for (uint32_t i = 0; i < n_words; ++i) b2s_store_le32(p + 4 * i, w[i]);
+}
+
+// InitialChainKey and InitialHash of init() (noise.go:91-94)
+void initial(uint8_t chain[32], uint8_t hash[32]) {
+  blake2s_bytes(nullptr, 0, (const uint8_t*)kNoiseConstruction, sizeof kNoiseConstruction - 1, 32, chain);
+  uint8_t in[32 + sizeof kWGIdentifier - 1];
+  memcpy(in, chain, 32);
+  memcpy(in + 32, kWGIdentifier, sizeof kWGIdentifier - 1);
+  blake2s_bytes(nullptr, 0, in, sizeof in, 32, hash);
+}
+
+// mixHash(InitialHash, pub) and InitialChainKey: where both sides start for the static key pub (:358, :415)
+void start_of(const uint32_t pub[8], uint32_t hash0[8], uint32_t chain0[8]) {
+  uint8_t chain[32], hash[32];
+  initial(chain, hash);
+  words_of(chain, 8, chain0);
+  words_of(hash, 8, hash0);
+  const uint32_t data[12] = {pub[0], pub[1], pub[2], pub[3], pub[4], pub[5], pub[6], pub[7], 0, 0, 0, 0};
+  noise_mix_hash(hash0, data, 32);
+}
+
+const uint32_t kBasePoint[8] = {9, 0, 0, 0, 0, 0, 0, 0};
+
+}  // namespace
+
+extern "C" {
+
+int wgcs_x25519(uint8_t out[32], const uint8_t scalar[32], const uint8_t point[32]) {
+  if (!out || !scalar || !point) return WGCS_ERR_INVALID_ARG;
+  uint32_t k[8], u[8], r[8];
+  words_of(scalar, 8, k);
+  words_of(point, 8, u);
+  const bool ok = x25519_words(k, u, r);
+  bytes_of(r, 8, out);
+  return ok ? WGCS_OK : WGCS_ERR_LOW_ORDER;
+}
+
+int wgcs_noise_responder_init(wgcs_noise_responder* r, const uint8_t private_key[32], uint8_t public_key[32]) {
+  if (!r || !private_key) return WGCS_ERR_INVALID_ARG;
+  uint32_t k[8], pub[8], hash0[8], chain0[8];
+  words_of(private_key, 8, k);
+  x25519_words(k, kBasePoint, pub);  // publicKey(), noise_helpers.go:83-89
+  start_of(pub, hash0, chain0);
+  memmove(r->private_key, private_key, 32);
+  bytes_of(hash0, 8, r->hash0);
+  bytes_of(chain0, 8, r->chain0);
+  if (public_key) bytes_of(pub, 8, public_key);
+  return WGCS_OK;
+}
+
+int wgcs_peer_keys_build(const wgcs_noise_responder* r, const uint8_t* public_keys, const uint32_t* peers,
+                         const uint32_t* flags, uint32_t n, wgcs_peer_key* table) {
+  if (n == 0) return WGCS_OK;
+  if (!r || !public_keys || !peers || !table) return WGCS_ERR_INVALID_ARG;
+  std::vector<uint32_t> order(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (peers[i] == WGCS_PEER_NONE) return WGCS_ERR_INVALID_ARG;
+    order[i] = i;
+  }
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    return memcmp(public_keys + 32 * (size_t)a, public_keys + 32 * (size_t)b, 32) < 0;
+  });
+  for (uint32_t i = 1; i < n; ++i)
+    if (memcmp(public_keys + 32 * (size_t)order[i - 1], public_keys + 32 * (size_t)order[i], 32) == 0)
+      return WGCS_ERR_INVALID_ARG;
+  uint32_t k[8];
+  words_of(r->private_key, 8, k);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint8_t* const pub = public_keys + 32 * (size_t)order[i];
+    uint32_t u[8], shared[8];
+    words_of(pub, 8, u);
+    x25519_words(k, u, shared);  // all zero where the key is a low-order point: the row never authenticates
+    wgcs_peer_key* const row = table + i;
+    memcpy(row->public_key, pub, 32);
+    bytes_of(shared, 8, row->shared);
+    row->peer = peers[order[i]];
+    row->flags = flags ? flags[order[i]] : WGCS_PEER_RUNNING;
+  }
+  return WGCS_OK;
+}
+
+int wgcs_peer_keys_find(const wgcs_peer_key* table, uint32_t n, const uint8_t public_key[32]) {
+  if (!public_key || (n && !table)) return -1;
+  uint32_t key[8];
+  words_of(public_key, 8, key);
+  return noise_find_peer(table, n, key);
+}
+
+int wgcs_noise_consume_initiation(const wgcs_noise_responder* r, const wgcs_peer_key* table, uint32_t n_peers,
+                                  const uint8_t* msg, size_t len, wgcs_hs_init* out) {
+  if (!r || !msg || !out || (n_peers && !table) || len != kNoiseInitiationSize) return WGCS_ERR_INVALID_ARG;
+  uint32_t k[8], hash0[8], chain0[8], m[kNoiseBodyWords], o[kHsInitWords];
+  words_of(r->private_key, 8, k);
+  words_of(r->hash0, 8, hash0);
+  words_of(r->chain0, 8, chain0);
+  words_of(msg, kNoiseBodyWords, m);
+  const int verdict = noise_consume_initiation(k, hash0, chain0, table, n_peers, m, o);
+  if (verdict == WGCS_ERR_INVALID_ARG) return verdict;
+  out->peer = o[0];
+  out->sender = o[1];
+  bytes_of(o + 2, 3, out->timestamp);
+  bytes_of(o + 5, 3, out->pad);
+  bytes_of(o + 8, 8, out->hash);
+  bytes_of(o + 16, 8, out->chain_key);
+  bytes_of(o + 24, 8, out->ephemeral);
+  return verdict;
+}
+
+int wgcs_noise_create_initiation(const uint8_t static_private[32], const uint8_t remote_static[32],
+                                 const uint8_t ephemeral_private[32], const uint8_t timestamp[12], uint32_t sender,
+                                 uint8_t msg[148], uint8_t hash[32], uint8_t chain_key[32]) {
+  if (!static_private || !remote_static || !ephemeral_private || !timestamp || !msg) return WGCS_ERR_INVALID_ARG;
+  uint32_t sk[8], spub[8], remote[8], ek[8], ts[3], hash0[8], chain0[8], m[37], h[8], c[8];
+  words_of(static_private, 8, sk);
+  words_of(remote_static, 8, remote);
+  words_of(ephemeral_private, 8, ek);
+  words_of(timestamp, 3, ts);
+  x25519_words(sk, kBasePoint, spub);  // d.keys.publicKey
+  start_of(remote, hash0, chain0);
+  const int rc = noise_create_initiation(sk, spub, remote, hash0, chain0, ek, ts, sender, m, h, c);
+  if (rc != WGCS_OK) {
+    memset(msg, 0, kNoiseInitiationSize);
+    return rc;
+  }
+  bytes_of(m, 37, msg);
+  if (hash) bytes_of(h, 8, hash);
+  if (chain_key) bytes_of(c, 8, chain_key);
+  return WGCS_OK;
+}
+
+}  // extern "C"

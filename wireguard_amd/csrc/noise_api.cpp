@@ -1,0 +1,61 @@
+// noise_api.cpp -- C ABI of the device-resident X25519 and handshake consume (include/wgcsum.h):
+//   wgcs_x25519_batch               curve25519.X25519, one per row     device/noise_helpers.go:93-105
+//   wgcs_handshake_consume_batch    ConsumeMessageInitiation to :457   device/noise.go:405-457
+// They run in noise_kernels.hip; the responder, the peer table and the rows
+// are the caller's device memory.  The host functions of the same section are
+// in noise.cpp.
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+
+#include "../../include/wgcsum.h"
+#include "wgcs_ctx.h"
+#include "wgcs_kernels.h"
+
+using namespace wgcs;
+
+namespace {
+
+constexpr uint32_t kMaxBatch = 1u << 28;  // rows are counted in 32 bits
+
+}  // namespace
+
+extern "C" {
+
+int wgcs_x25519_batch(wgcs_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_points, uint32_t n, uint8_t* d_out,
+                      int32_t* d_status, void* stream) {
+  if (!ctx) return WGCS_ERR_INVALID_ARG;
+  if (n == 0) return WGCS_OK;
+  if (!d_scalars || !d_points || !d_out || !d_status) return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
+  if (n > kMaxBatch || ((uintptr_t)d_scalars & 3) || ((uintptr_t)d_points & 3) || ((uintptr_t)d_out & 3) ||
+      ((uintptr_t)d_status & 3))
+    return set_err(ctx, WGCS_ERR_INVALID_ARG, "n <= 2^28, 4-byte aligned d_scalars / d_points / d_out / d_status");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  hipSetDevice(ctx->device);
+  const hipError_t e =
+      launch_x25519(d_scalars, d_points, n, d_out, d_status, stream ? (hipStream_t)stream : ctx->stream);
+  return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "x25519 launch");
+}
+
+int wgcs_handshake_consume_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const wgcs_aead_pkt* d_pkts,
+                                 const int32_t* d_type, const int32_t* d_gate, uint32_t n,
+                                 const wgcs_noise_responder* d_responder, const wgcs_peer_key* d_table,
+                                 uint32_t n_peers, int32_t* d_verdict, wgcs_hs_init* d_out, void* stream) {
+  if (!ctx) return WGCS_ERR_INVALID_ARG;
+  if (n == 0) return WGCS_OK;
+  if (!d_arena || !d_pkts || !d_type || !d_responder || !d_verdict || !d_out || (n_peers && !d_table))
+    return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
+  if (d_gate == d_verdict) return set_err(ctx, WGCS_ERR_INVALID_ARG, "d_verdict must not be d_gate");
+  if (n > kMaxBatch || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_type & 3) || ((uintptr_t)d_gate & 3) ||
+      ((uintptr_t)d_responder & 3) || ((uintptr_t)d_table & 3) || ((uintptr_t)d_verdict & 3) || ((uintptr_t)d_out & 3))
+    return set_err(ctx, WGCS_ERR_INVALID_ARG,
+                   "n <= 2^28, 8-byte aligned d_pkts, 4-byte aligned d_type / d_gate / d_responder / d_table / "
+                   "d_verdict / d_out");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  hipSetDevice(ctx->device);
+  const hipError_t e = launch_hs_consume(d_arena, d_pkts, d_type, d_gate, n, d_responder, d_table, n_peers, d_verdict,
+                                         d_out, stream ? (hipStream_t)stream : ctx->stream);
+  return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "handshake_consume launch");
+}
+
+}  // extern "C"

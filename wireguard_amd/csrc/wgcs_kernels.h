@@ -89,4 +89,13 @@ hipError_t launch_hs_screen(const uint8_t* arena, const wgcs_aead_pkt* pkts, con
                             const wgcs_cookie_checker* checker, const wgcs_src_addr* srcs, uint32_t under_load,
                             const uint8_t* nonces, int32_t* verdict, uint8_t* replies, hipStream_t s);
 
+// Curve25519 and the consumption of screened initiations (noise_kernels.hip):
+// one lane per row; gate may be NULL.
+hipError_t launch_x25519(const uint8_t* scalars, const uint8_t* points, uint32_t n, uint8_t* out, int32_t* status,
+                         hipStream_t s);
+hipError_t launch_hs_consume(const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* types,
+                             const int32_t* gate, uint32_t n, const wgcs_noise_responder* responder,
+                             const wgcs_peer_key* table, uint32_t n_peers, int32_t* verdict, wgcs_hs_init* out,
+                             hipStream_t s);
+
 }  // namespace wgcs

@@ -1,0 +1,337 @@
+// wgcs_noise.h -- the scalar steps of the reference's Noise_IKpsk2 handshake up
+// to the consumption of an initiation (device/noise.go:91-94, :324-457,
+// device/noise_helpers.go:18-58), shared by hs_consume_kernel
+// (noise_kernels.hip), the host functions of noise.cpp and
+// tests/noise_host/noise_host.cpp.
+//
+// Everything is little-endian words in registers: a hash, a chaining key, a
+// key, a public key and a shared secret are 8 words, a message is its 37.
+//   mixHash(h, data)   = BLAKE2s-256(h | data)                       noise.go:332-338
+//   mixKey(c, data)    = KDF1(c, data)                               :340-342
+//   HMAC               = HMAC over unkeyed BLAKE2s-256, 64-byte block, noise_helpers.go:18-35
+//                        (not keyed BLAKE2s); every key of the handshake is 32 bytes
+//   KDF1 / KDF2 / KDF3 = HKDF (RFC 5869) with that HMAC              :37-58
+//   the AEAD           = ChaCha20-Poly1305 (RFC 8439 §2.8) under the zero nonce
+//                        with the 32-byte hash as additional data and a text
+//                        of 32 (a static key), 12 (a timestamp) or 0 bytes
+// Inputs of the hash are zero-padded word arrays with a byte length; every
+// length is a constant where the kernel calls, so the block loops unroll and
+// nothing is indexed at run time (the rule of wgcs_blake2s.h).
+//
+// An initiation (MessageInitiation, noise.go:100-125) in words:
+//   0 type | 1 sender | 2..9 ephemeral | 10..17 static ct | 18..21 its tag |
+//   22..24 timestamp ct | 25..28 its tag | 29..32 MAC1 | 33..36 MAC2
+#pragma once
+
+#include <stdint.h>
+
+#include "../../include/wgcsum.h"
+#include "wgcs_blake2s.h"
+#include "wgcs_x25519.h"
+#include "wgcs_xchacha.h"
+
+namespace wgcs {
+
+constexpr uint32_t kNoiseInitiationSize = 148;  // MessageInitiationSize, noise.go:60
+constexpr uint32_t kNoiseInitiationType = 1;    // MessageInitiationType
+constexpr uint32_t kNoiseBodyWords = 29;        // everything before MAC1: what ConsumeMessageInitiation reads
+
+// BLAKE2s-256, unkeyed, of the first len <= 128 bytes of in (zero-padded words)
+WGCS_HD void noise_hash(const uint32_t in[32], uint32_t len, uint32_t h[8]) {
+  h[0] = kB2sIv0 ^ 0x01010020u;  // §2.5: digest 32, no key, fanout 1, depth 1
+  h[1] = kB2sIv1;
+  h[2] = kB2sIv2;
+  h[3] = kB2sIv3;
+  h[4] = kB2sIv4;
+  h[5] = kB2sIv5;
+  h[6] = kB2sIv6;
+  h[7] = kB2sIv7;
+  if (len <= 64) {
+    blake2s_compress(h, in, len, true);
+  } else {
+    blake2s_compress(h, in, 64, false);
+    blake2s_compress(h, in + 16, len, true);
+  }
+}
+
+// mixHash (noise.go:332-338): h = BLAKE2s-256(h | data), data of len <= 48 bytes
+WGCS_HD void noise_mix_hash(uint32_t h[8], const uint32_t data[12], uint32_t len) {
+  uint32_t in[32];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) in[i] = h[i];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) in[8 + i] = data[i];
+#pragma unroll
+  for (int i = 20; i < 32; ++i) in[i] = 0;
+  noise_hash(in, 32 + len, h);
+}
+
+// HMAC1 (noise_helpers.go:18-25): HMAC-BLAKE2s-256 of len <= 64 bytes under a 32-byte key
+WGCS_HD void noise_hmac1(const uint32_t key[8], const uint32_t data[16], uint32_t len, uint32_t out[8]) {
+  uint32_t in[32], inner[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) in[i] = key[i] ^ 0x36363636u;  // ipad
+#pragma unroll
+  for (int i = 8; i < 16; ++i) in[i] = 0x36363636u;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) in[16 + i] = data[i];
+  noise_hash(in, 64 + len, inner);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) in[i] = key[i] ^ 0x5c5c5c5cu;  // opad
+#pragma unroll
+  for (int i = 8; i < 16; ++i) in[i] = 0x5c5c5c5cu;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) in[16 + i] = inner[i];
+#pragma unroll
+  for (int i = 24; i < 32; ++i) in[i] = 0;
+  noise_hash(in, 96, out);
+}
+
+// HMAC2 (:27-35) as the KDFs use it: the 32 bytes of in0, then the one byte in1
+WGCS_HD void noise_hmac2(const uint32_t key[8], const uint32_t in0[8], uint32_t in1, uint32_t out[8]) {
+  const uint32_t data[16] = {in0[0], in0[1], in0[2], in0[3], in0[4], in0[5], in0[6], in0[7], in1 & 0xFFu,
+                             0,      0,      0,      0,      0,      0,      0};
+  noise_hmac1(key, data, 33, out);
+}
+
+// the expansion of KDF1 / KDF2 / KDF3 under the pseudo-random key prk
+WGCS_HD void noise_kdf_first(const uint32_t prk[8], uint32_t t0[8]) {
+  const uint32_t one[16] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  noise_hmac1(prk, one, 1, t0);
+}
+
+// KDF1 (:37-40), input of len <= 64 bytes; t0 may be key
+WGCS_HD void noise_kdf1(uint32_t t0[8], const uint32_t key[8], const uint32_t input[16], uint32_t len) {
+  uint32_t prk[8];
+  noise_hmac1(key, input, len, prk);
+  noise_kdf_first(prk, t0);
+}
+
+// KDF2 (:42-49); t0 may be key
+WGCS_HD void noise_kdf2(uint32_t t0[8], uint32_t t1[8], const uint32_t key[8], const uint32_t input[16], uint32_t len) {
+  uint32_t prk[8];
+  noise_hmac1(key, input, len, prk);
+  noise_kdf_first(prk, t0);
+  noise_hmac2(prk, t0, 2, t1);
+}
+
+// KDF3 (:51-58); t0 may be key
+WGCS_HD void noise_kdf3(uint32_t t0[8], uint32_t t1[8], uint32_t t2[8], const uint32_t key[8], const uint32_t input[16],
+                        uint32_t len) {
+  uint32_t prk[8];
+  noise_hmac1(key, input, len, prk);
+  noise_kdf_first(prk, t0);
+  noise_hmac2(prk, t0, 2, t1);
+  noise_hmac2(prk, t1, 3, t2);
+}
+
+// KDF1 / KDF2 of a 32-byte input, the only size the handshake feeds them
+WGCS_HD void noise_pad32(const uint32_t in[8], uint32_t out[16]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) out[i] = in[i];
+#pragma unroll
+  for (int i = 8; i < 16; ++i) out[i] = 0;
+}
+
+// mixKey (noise.go:340-342) of 32 bytes
+WGCS_HD void noise_mix_key(uint32_t chain[8], const uint32_t data[8]) {
+  uint32_t in[16];
+  noise_pad32(data, in);
+  noise_kdf1(chain, chain, in, 32);
+}
+
+// KDF2(&chain, &key, chain[:], secret[:]) of noise.go:371-376, :384-389, :425, :444-449
+WGCS_HD void noise_mix_secret(uint32_t chain[8], uint32_t key[8], const uint32_t secret[8]) {
+  uint32_t in[16];
+  noise_pad32(secret, in);
+  noise_kdf2(chain, key, chain, in, 32);
+}
+
+// The Poly1305 tag of RFC 8439 §2.8 over ad (32 bytes) | ct (n <= 32 bytes, a multiple of 4,
+// zero-padded: pad16 is part of the construction) | LE64(32) | LE64(n), under the one-time key.
+WGCS_HD void noise_aead_tag(const uint32_t otk[8], const uint32_t ad[8], const uint32_t ct[8], uint32_t n,
+                            uint32_t tag[4]) {
+  const P1305 r = p1305_clamp_r(otk[0], otk[1], otk[2], otk[3]);
+  P1305 h = p1305_mul(p1305_from_words(ad[0], ad[1], ad[2], ad[3], 1), r);
+  h = p1305_mul(p1305_add(h, p1305_from_words(ad[4], ad[5], ad[6], ad[7], 1)), r);
+  if (n > 0) h = p1305_mul(p1305_add(h, p1305_from_words(ct[0], ct[1], ct[2], ct[3], 1)), r);
+  if (n > 16) h = p1305_mul(p1305_add(h, p1305_from_words(ct[4], ct[5], ct[6], ct[7], 1)), r);
+  h = p1305_mul(p1305_add(h, p1305_from_words(32, 0, n, 0, 1)), r);
+  p1305_finish(h, otk[4], otk[5], otk[6], otk[7], tag);
+}
+
+// aead.Seal(dst[:0], ZeroNonce[:], pt, ad): ct (n bytes as words, zero past them) and tag
+WGCS_HD void noise_seal(const uint32_t key[8], const uint32_t pt[8], uint32_t n, const uint32_t ad[8], uint32_t ct[8],
+                        uint32_t tag[4]) {
+  uint32_t otk[8], ks[8];
+  chacha20_block_head(key, 0, 0, 0, otk);
+  chacha20_block_head(key, 1, 0, 0, ks);
+#pragma unroll
+  for (uint32_t i = 0; i < 8; ++i) ct[i] = 4 * i < n ? pt[i] ^ ks[i] : 0u;
+  noise_aead_tag(otk, ad, ct, n, tag);
+}
+
+// aead.Open: true and the plaintext when the tag matches (an OR of XORs over all 16 bytes);
+// pt is written either way and means nothing on false.  ct is zero past its n bytes.
+WGCS_HD bool noise_open(const uint32_t key[8], const uint32_t ct[8], uint32_t n, const uint32_t tag[4],
+                        const uint32_t ad[8], uint32_t pt[8]) {
+  uint32_t otk[8], ks[8], want[4];
+  chacha20_block_head(key, 0, 0, 0, otk);
+  chacha20_block_head(key, 1, 0, 0, ks);
+  noise_aead_tag(otk, ad, ct, n, want);
+#pragma unroll
+  for (uint32_t i = 0; i < 8; ++i) pt[i] = 4 * i < n ? ct[i] ^ ks[i] : 0u;
+  return tag16_equal(want, tag);
+}
+
+// eight words of a table row's key or secret
+WGCS_HD void noise_row_words(const uint8_t* p, uint32_t w[8]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t* const d = (const uint32_t*)p;  // rows are 4-byte aligned on the device
+#pragma unroll
+  for (int i = 0; i < 8; ++i) w[i] = d[i];
+#else
+  b2s_key_words(p, 32, w);
+#endif
+}
+
+WGCS_HD uint32_t noise_bswap(uint32_t x) {
+  return (x << 24) | ((x & 0xFF00u) << 8) | ((x >> 8) & 0xFF00u) | (x >> 24);
+}
+
+// memcmp of two 32-byte strings held as little-endian words: -1, 0 or 1
+WGCS_HD int noise_key_cmp(const uint32_t a[8], const uint32_t b[8]) {
+  int r = 0;
+#pragma unroll
+  for (int i = 7; i >= 0; --i) {  // the lowest word that differs decides: later ones are overridden
+    const uint32_t x = noise_bswap(a[i]), y = noise_bswap(b[i]);
+    r = x < y ? -1 : x > y ? 1 : r;
+  }
+  return r;
+}
+
+// GetPeer (device.go) over the table of wgcs_peer_keys_build, rows sorted by public key:
+// the row of key, or -1.  At most ceil(log2(n + 1)) probes.
+WGCS_HD int32_t noise_find_peer(const wgcs_peer_key* table, uint32_t n, const uint32_t key[8]) {
+  uint32_t lo = 0, hi = n;  // the first row >= key lies in [lo, hi]
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    uint32_t row[8];
+    noise_row_words(table[mid].public_key, row);
+    if (noise_key_cmp(row, key) < 0) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo >= n) return -1;
+  uint32_t row[8];
+  noise_row_words(table[lo].public_key, row);
+  return noise_key_cmp(row, key) == 0 ? (int32_t)lo : -1;
+}
+
+// The words of wgcs_hs_init: 0 peer | 1 sender | 2..4 timestamp | 5..7 pad |
+// 8..15 hash | 16..23 chain_key | 24..31 ephemeral.
+constexpr uint32_t kHsInitWords = 32;
+
+// ConsumeMessageInitiation up to the replay / flood check (noise.go:405-457)
+// for the message words m under the responder's private key, hash0 =
+// mixHash(InitialHash, its public key) (:415) and chain0 = InitialChainKey.
+// Returns the verdict of wgcs_handshake_consume_batch and fills o as that
+// function's table says: untouched for WGCS_ERR_INVALID_ARG, the whole row for
+// WGCS_HS_CONSUMED, else zero but for the sender and the peer found so far.
+WGCS_HD int noise_consume_initiation(const uint32_t priv[8], const uint32_t hash0[8], const uint32_t chain0[8],
+                                     const wgcs_peer_key* table, uint32_t n_peers, const uint32_t m[kNoiseBodyWords],
+                                     uint32_t o[kHsInitWords]) {
+  if (m[0] != kNoiseInitiationType) return WGCS_ERR_INVALID_ARG;  // :406-408
+#pragma unroll
+  for (uint32_t i = 0; i < kHsInitWords; ++i) o[i] = 0;
+  o[0] = WGCS_PEER_NONE;
+  o[1] = m[1];
+  uint32_t hash[8], chain[8], key[8], eph[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    hash[i] = hash0[i];
+    chain[i] = chain0[i];
+    eph[i] = m[2 + i];
+  }
+  const uint32_t eph12[12] = {eph[0], eph[1], eph[2], eph[3], eph[4], eph[5], eph[6], eph[7], 0, 0, 0, 0};
+  noise_mix_hash(hash, eph12, 32);  // :416
+  noise_mix_key(chain, eph);        // :417
+  // decrypt static key
+  uint32_t shared[8];
+  if (!x25519_words(priv, eph, shared)) return WGCS_ERR_LOW_ORDER;  // :421-424
+  noise_mix_secret(chain, key, shared);                              // :425
+  uint32_t peer_pub[8];
+  if (!noise_open(key, m + 10, 32, m + 18, hash, peer_pub)) return WGCS_ERR_AUTH;  // :427-430
+  noise_mix_hash(hash, m + 10, 48);                                                 // :431
+  const int32_t row = noise_find_peer(table, n_peers, peer_pub);                    // :432
+  if (row < 0) return WGCS_ERR_NO_PEER;
+  o[0] = table[row].peer;
+  if (!(table[row].flags & 1u)) return WGCS_ERR_NO_PEER;  // :433-435: !peer.isRunning
+  // verify identity
+  noise_row_words(table[row].shared, shared);
+  if ((shared[0] | shared[1] | shared[2] | shared[3] | shared[4] | shared[5] | shared[6] | shared[7]) == 0)
+    return WGCS_ERR_NO_PEER;                // :440-443: isZero(precomputedSharedSecret)
+  noise_mix_secret(chain, key, shared);     // :444-449
+  const uint32_t ts_ct[8] = {m[22], m[23], m[24], 0, 0, 0, 0, 0};
+  uint32_t ts[8];
+  if (!noise_open(key, ts_ct, 12, m + 25, hash, ts)) return WGCS_ERR_AUTH;  // :451-455
+  const uint32_t ts_field[12] = {m[22], m[23], m[24], m[25], m[26], m[27], m[28], 0, 0, 0, 0, 0};
+  noise_mix_hash(hash, ts_field, 28);  // :456
+  o[2] = ts[0];
+  o[3] = ts[1];
+  o[4] = ts[2];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    o[8 + i] = hash[i];
+    o[16 + i] = chain[i];
+    o[24 + i] = eph[i];
+  }
+  return WGCS_HS_CONSUMED;
+}
+
+// CreateMessageInitiation (noise.go:344-403) with the caller's ephemeral private key,
+// timestamp and sender index: the 37 words of the message with zero MACs, and the handshake's
+// hash and chaining key after it.  hash0 = mixHash(InitialHash, remote static) (:358), chain0 =
+// InitialChainKey; static_pub is the sender's own public key.  WGCS_ERR_LOW_ORDER where either
+// shared secret is zero (:366-369, :381-383), m then means nothing.
+WGCS_HD int noise_create_initiation(const uint32_t static_priv[8], const uint32_t static_pub[8],
+                                    const uint32_t remote_static[8], const uint32_t hash0[8],
+                                    const uint32_t chain0[8], const uint32_t eph_priv[8], const uint32_t ts[3],
+                                    uint32_t sender, uint32_t m[37], uint32_t hash[8], uint32_t chain[8]) {
+  const uint32_t base[8] = {9, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t eph[8], key[8], shared[8];
+#pragma unroll
+  for (int i = 0; i < 37; ++i) m[i] = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    hash[i] = hash0[i];
+    chain[i] = chain0[i];
+  }
+  x25519_words(eph_priv, base, eph);  // :361
+  m[0] = kNoiseInitiationType;
+  m[1] = sender;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) m[2 + i] = eph[i];
+  noise_mix_key(chain, eph);  // :363
+  const uint32_t eph12[12] = {eph[0], eph[1], eph[2], eph[3], eph[4], eph[5], eph[6], eph[7], 0, 0, 0, 0};
+  noise_mix_hash(hash, eph12, 32);  // :364
+  // encrypt static key
+  if (!x25519_words(eph_priv, remote_static, shared)) return WGCS_ERR_LOW_ORDER;  // :366-369
+  noise_mix_secret(chain, key, shared);                                            // :371-376
+  noise_seal(key, static_pub, 32, hash, m + 10, m + 18);                           // :378
+  noise_mix_hash(hash, m + 10, 48);                                                // :379
+  // encrypt timestamp
+  if (!x25519_words(static_priv, remote_static, shared)) return WGCS_ERR_LOW_ORDER;  // :381-383
+  noise_mix_secret(chain, key, shared);                                               // :384-389
+  const uint32_t ts_pt[8] = {ts[0], ts[1], ts[2], 0, 0, 0, 0, 0};
+  uint32_t ts_ct[8], ts_tag[4];
+  noise_seal(key, ts_pt, 12, hash, ts_ct, ts_tag);  // :392
+  m[22] = ts_ct[0];
+  m[23] = ts_ct[1];
+  m[24] = ts_ct[2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) m[25 + i] = ts_tag[i];
+  noise_mix_hash(hash, m + 22, 28);  // :400: m[29..33] are still zero
+  return WGCS_OK;
+}
+
+}  // namespace wgcs

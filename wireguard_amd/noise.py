@@ -1,0 +1,143 @@
+"""Host-side mirror of X25519 and of the stateless part of the reference's
+Noise handshake (package `device`, noise.go and noise_helpers.go) over the C ABI.
+
+Names and argument meaning follow the reference:
+  x25519(scalar, point)                           curve25519.X25519, noise_helpers.go:93-105
+  responder_init(private)                         d.keys and the first mixHash, noise.go:91-94, :415
+  peer_keys_build(responder, keys, peers, flags)  the table GetPeer reads, with precomputedSharedSecret, :305, :432
+  consume_initiation                              ConsumeMessageInitiation up to the replay / flood check, :405-457
+  create_initiation                               CreateMessageInitiation, :344-403
+  x25519_batch / consume_batch                    the same over device-resident rows
+The clock, the randomness and the handshake state are the caller's: the
+ephemeral private key, the timestamp and the sender index are arguments, and
+what follows noise.go:457 -- the comparison with lastTimestamp, the flood rule,
+the state update -- takes a HS_INIT_DTYPE row and stays with the host.
+Curve25519, the HMAC / HKDF layer, the AEAD and the kernels live in
+libwgcsum.so (wgcs_x25519.h, wgcs_noise.h, noise_kernels.hip); nothing here
+computes.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import ERR_AUTH, ERR_LOW_ORDER, ERR_NO_PEER, HS_CONSUMED, HS_NONE, HS_PASS, PEER_NONE, PEER_RUNNING
+from .cookie import _fixed, _status
+from .transport import AEAD_PKT_DTYPE, _rows
+from .tun import _ptr
+
+NOISE_RESPONDER_DTYPE = np.dtype([("private_key", "u1", (32,)), ("hash0", "u1", (32,)),
+                                  ("chain0", "u1", (32,))])  # wgcs_noise_responder
+PEER_KEY_DTYPE = np.dtype([("public_key", "u1", (32,)), ("shared", "u1", (32,)), ("peer", "<u4"),
+                           ("flags", "<u4")])  # wgcs_peer_key
+HS_INIT_DTYPE = np.dtype([("peer", "<u4"), ("sender", "<u4"), ("timestamp", "u1", (12,)), ("pad", "u1", (12,)),
+                          ("hash", "u1", (32,)), ("chain_key", "u1", (32,)), ("ephemeral", "u1", (32,))])  # wgcs_hs_init
+assert NOISE_RESPONDER_DTYPE.itemsize == 96 and PEER_KEY_DTYPE.itemsize == 72 and HS_INIT_DTYPE.itemsize == 128
+
+__all__ = ["NOISE_RESPONDER_DTYPE", "PEER_KEY_DTYPE", "HS_INIT_DTYPE", "x25519", "responder_init", "peer_keys_build",
+           "peer_keys_find", "consume_initiation", "create_initiation", "x25519_batch", "consume_batch", "HS_NONE",
+           "HS_PASS", "HS_CONSUMED", "ERR_AUTH", "ERR_LOW_ORDER", "ERR_NO_PEER", "PEER_NONE", "PEER_RUNNING"]
+
+
+def _one(x, dtype: np.dtype, what: str) -> np.ndarray:
+    a = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+    if len(a) != 1:
+        raise ValueError(f"one {what} row")
+    return a
+
+
+def x25519(scalar, point) -> bytes | None:
+    """X25519(scalar, point), or None for the all-zero result of a low-order point."""
+    out = C.create_string_buffer(32)
+    rc = _lib.load().wgcs_x25519(out, _fixed(scalar, 32, "a scalar"), _fixed(point, 32, "a point"))
+    if rc == ERR_LOW_ORDER:
+        return None
+    _status(rc, "wgcs_x25519")
+    return out.raw
+
+
+def responder_init(private_key) -> tuple[np.ndarray, bytes]:
+    """(one NOISE_RESPONDER_DTYPE row for the static private key, its public key)."""
+    r = np.zeros(1, NOISE_RESPONDER_DTYPE)
+    pub = C.create_string_buffer(32)
+    _status(_lib.load().wgcs_noise_responder_init(r.ctypes.data, _fixed(private_key, 32, "a private key"), pub),
+            "wgcs_noise_responder_init")
+    return r, pub.raw
+
+
+def peer_keys_build(responder, public_keys, peers, flags=None) -> np.ndarray:
+    """PEER_KEY_DTYPE rows sorted by public key for the peers' 32-byte static
+    public keys, their ids and (optional; default: all running) flags."""
+    r = _one(responder, NOISE_RESPONDER_DTYPE, "NOISE_RESPONDER_DTYPE")
+    keys = b"".join(_fixed(k, 32, "a public key") for k in public_keys)
+    n = len(keys) // 32
+    ids = np.ascontiguousarray(peers, dtype=np.uint32).reshape(-1)
+    fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint32).reshape(-1)
+    if len(ids) != n or (fl is not None and len(fl) != n):
+        raise ValueError("one peer id (and one flags word) per public key")
+    table = np.zeros(n, PEER_KEY_DTYPE)
+    _status(_lib.load().wgcs_peer_keys_build(r.ctypes.data, keys, ids.ctypes.data if n else None,
+                                             None if fl is None or n == 0 else fl.ctypes.data, n,
+                                             table.ctypes.data if n else None), "wgcs_peer_keys_build")
+    return table
+
+
+def peer_keys_find(table, public_key) -> int:
+    """The row of public_key in a PEER_KEY_DTYPE table, or -1."""
+    t = np.ascontiguousarray(table, dtype=PEER_KEY_DTYPE).reshape(-1)
+    return _lib.load().wgcs_peer_keys_find(t.ctypes.data if len(t) else None, len(t),
+                                           _fixed(public_key, 32, "a public key"))
+
+
+def consume_initiation(responder, table, msg) -> tuple[int, np.ndarray]:
+    """(verdict, one HS_INIT_DTYPE row) for one message on the host: HS_CONSUMED
+    with the whole row, or ERR_LOW_ORDER / ERR_AUTH / ERR_NO_PEER with a row
+    that holds the sender and the peer found so far, or ERR_INVALID_ARG (a
+    length other than 148 or a wrong type word) with the row untouched (zero)."""
+    r = _one(responder, NOISE_RESPONDER_DTYPE, "NOISE_RESPONDER_DTYPE")
+    t = np.ascontiguousarray(table, dtype=PEER_KEY_DTYPE).reshape(-1)
+    m = bytes(msg)
+    out = np.zeros(1, HS_INIT_DTYPE)
+    verdict = _lib.load().wgcs_noise_consume_initiation(r.ctypes.data, t.ctypes.data if len(t) else None, len(t), m,
+                                                        len(m), out.ctypes.data)
+    return verdict, out
+
+
+def create_initiation(static_private, remote_static, ephemeral_private, timestamp, sender: int
+                      ) -> tuple[bytes, bytes, bytes]:
+    """(the 148-byte initiation with zero MACs -- cookie.add_macs fills them --,
+    the handshake's hash, its chaining key)."""
+    msg, h, ck = C.create_string_buffer(148), C.create_string_buffer(32), C.create_string_buffer(32)
+    _status(_lib.load().wgcs_noise_create_initiation(_fixed(static_private, 32, "a private key"),
+                                                     _fixed(remote_static, 32, "a public key"),
+                                                     _fixed(ephemeral_private, 32, "an ephemeral private key"),
+                                                     _fixed(timestamp, 12, "a timestamp"), sender & 0xFFFFFFFF, msg, h,
+                                                     ck), "wgcs_noise_create_initiation")
+    return msg.raw, h.raw, ck.raw
+
+
+def x25519_batch(dev, scalars, points, out, status, stream=None, n: int | None = None) -> None:
+    """Asynchronous wgcs_x25519_batch over 32-byte rows on the device: out row q
+    = X25519(scalars row q, points row q), status[q] (int32) = 0 or ERR_LOW_ORDER."""
+    s = getattr(stream, "cuda_stream", stream)
+    if n is None:
+        n = scalars.numel() * scalars.element_size() // 32
+    dev._check(dev.lib.wgcs_x25519_batch(dev.h, _ptr(scalars), _ptr(points), n, _ptr(out), _ptr(status), s))
+
+
+def consume_batch(dev, arena, pkts, types, gate, responder, table, verdict, out, stream=None, n: int | None = None,
+                  n_peers: int | None = None) -> None:
+    """Asynchronous wgcs_handshake_consume_batch over classify_batch's pkts and
+    types and screen_batch's verdicts as `gate` (None: every row of type 1):
+    verdict[q] (int32) = HS_NONE, HS_CONSUMED, ERR_INVALID_ARG, ERR_LOW_ORDER,
+    ERR_AUTH or ERR_NO_PEER, and out (HS_INIT_DTYPE rows) as the header says.
+    responder is one NOISE_RESPONDER_DTYPE row and table PEER_KEY_DTYPE rows on
+    the device."""
+    s = getattr(stream, "cuda_stream", stream)
+    n = _rows(pkts, AEAD_PKT_DTYPE) if n is None else n
+    n_peers = (0 if table is None else _rows(table, PEER_KEY_DTYPE)) if n_peers is None else n_peers
+    dev._check(dev.lib.wgcs_handshake_consume_batch(dev.h, _ptr(arena), _ptr(pkts), _ptr(types), _ptr(gate), n,
+                                                    _ptr(responder), _ptr(table) if n_peers else None, n_peers,
+                                                    _ptr(verdict), _ptr(out), s))
