@@ -206,13 +206,33 @@ int wgcs_checksum_batch(wgcs_ctx *ctx, int mode, unsigned flags, uint8_t *d_aren
 
 /* A series of independent device-resident batches enqueued by one call (e.g.
  * consecutive Tun.Read/Write batches, tun/tun.go:477-508, :654-700, already in
- * HBM): batch k is launched on streams[k % n_streams] (n_streams 0: the
- * context's stream), in order, with wgcs_checksum_batch's semantics.  Optional
- * bracket events (hipEvent_t as void*, created by the caller): ev_begin is
- * recorded on streams[0] before the first launch and the other streams wait on
- * it before their first; after the last launch every other stream that got a
- * batch is joined to streams[0] and ev_end is recorded there, so the pair
- * spans every launch.
+ * HBM), each with wgcs_checksum_batch's semantics.  The list is dealt over
+ * streams[0 .. n_streams) (n_streams 0: the context's stream): batch k belongs
+ * to streams[k % n_streams].
+ *
+ * Promised:
+ *  - ordering against each listed stream's other work: batch k starts after
+ *    everything queued earlier on its stream (a copy that fills its arena),
+ *    and whatever is queued later on a listed stream that has a batch, or a
+ *    wait on such a stream, comes after EVERY batch of the call -- all results
+ *    are ready when any one of those streams is;
+ *  - with WGCS_F_INPLACE, batches k and k + n_streams run in list order (they
+ *    share a stream), as do all batches on one stream;
+ *  - two batches whose `out` ranges overlap without being the same (arena,
+ *    pkts, initial, out, n) tuple leave the later batch's results there;
+ *  - every batch of the list is read and summed in full, repeated ones too;
+ *  - optional bracket events (hipEvent_t as void*, created by the caller):
+ *    ev_begin is recorded on streams[0] before the first launch and ev_end on
+ *    streams[0] after the last, so the pair spans every launch.
+ * Not promised: that batch k physically runs on streams[k % n_streams], or any
+ * order between the batches of one call without WGCS_F_INPLACE.  Consecutive
+ * batches that may run concurrently are processed by one launch on streams[0]
+ * (up to 32 per launch, walking the batches in list order; the other listed
+ * streams are joined before it and forked after it).  WGCS_F_INPLACE, or the
+ * diagnostic switch WGCS_FUSE=0 in the environment at wgcs_init, keeps one
+ * launch per batch on streams[k % n_streams]: a listed stream's later work
+ * then follows that stream's own batches only, and ev_end, or a wait on every
+ * listed stream, covers them all.
  * All arguments are checked before anything is enqueued. */
 typedef struct wgcs_batch {
   uint8_t *arena;

@@ -15,6 +15,7 @@ the 128-byte lines the rows touch).
 usage: pmc_sized.py PMC_DIR [KERNEL_SUBSTR] -> one JSON line per kernel:
   median per launch of each counter, read_bytes, and the unsized remainder
   RDREQ - (128B + 64B + 32B) (0 when every request has one of the sizes).
+       pmc_sized.py each PMC_DIR [KERNEL_SUBSTR] -> one JSON line per dispatch.
        pmc_sized.py cal PMC_DIR PROBE_LOG -> the calibration probe's ratios."""
 import csv
 import glob
@@ -72,6 +73,12 @@ def cal(d, log):
 def main():
     if sys.argv[1] == "cal":
         return cal(sys.argv[2], sys.argv[3])
+    if sys.argv[1] == "each":  # one line per dispatch (launches of different sizes under one kernel name)
+        for name, launches in collect(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else "").items():
+            for disp, c in launches:
+                rd = 128 * c.get(NAMES[1], 0) + 64 * c.get(NAMES[2], 0) + 32 * c.get(NAMES[3], 0)
+                print(json.dumps({"kernel": name[:90], "dispatch": disp, "read_bytes": int(rd), **c}))
+        return
     d = sys.argv[1]
     sub = sys.argv[2] if len(sys.argv) > 2 else ""
     for name, launches in collect(d, sub).items():

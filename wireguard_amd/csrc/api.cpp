@@ -129,9 +129,11 @@ int wgcs_init(int device, wgcs_ctx** out) {
   // created inside a caller's timed enqueue
   for (int j = 1; j < WGCS_MAX_BATCH_STREAMS && e == hipSuccess; ++j)
     e = hipEventCreateWithFlags(&ctx->join_ev[j], hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming);
   if (e != hipSuccess) {
     for (hipEvent_t ev : ctx->join_ev)
       if (ev) hipEventDestroy(ev);
+    if (ctx->fork_ev) hipEventDestroy(ctx->fork_ev);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
     return WGCS_ERR_HIP;
@@ -149,6 +151,7 @@ int wgcs_init(int device, wgcs_ctx** out) {
   if (xc) ctx->tune.xcd = atoi(xc) ? 1 : 0;
   const char* al = getenv("WGCS_ALIGN");
   if (al && (atoi(al) == 16 || atoi(al) == 32 || atoi(al) == 64 || atoi(al) == 128)) ctx->tune.align = atoi(al);
+  ctx->fuse = batch_plan_fuse_env(getenv("WGCS_FUSE"));
   *out = ctx;
   return WGCS_OK;
 }
@@ -220,6 +223,7 @@ int wgcs_destroy(wgcs_ctx* ctx) {
   if (ctx->stream) hipStreamDestroy(ctx->stream);
   for (hipEvent_t ev : ctx->join_ev)
     if (ev) hipEventDestroy(ev);
+  if (ctx->fork_ev) hipEventDestroy(ctx->fork_ev);
   delete ctx;
   return WGCS_OK;
 }
@@ -297,9 +301,48 @@ int wgcs_checksum_batches(wgcs_ctx* ctx, int mode, unsigned flags, const wgcs_ba
   hipStream_t st[WGCS_MAX_BATCH_STREAMS];
   for (uint32_t j = 0; j < ns; ++j) st[j] = n_streams && streams[j] ? (hipStream_t)streams[j] : ctx->stream;
   hipError_t e = hipSuccess;
-  // ev_begin, then batch 0 at once (the first launch is the latency-critical
-  // one); each other stream waits on ev_begin just before its first launch
   if (ev_begin && (e = hipEventRecord((hipEvent_t)ev_begin, st[0])) != hipSuccess) return hip_fail(ctx, e, "ev_begin");
+  const BatchPlanCfg cfg = {(uint32_t)checksum_pkts_per_block(ctx->tune), (uint64_t)ctx->num_cu * ctx->tune.blocks_per_cu,
+                            ctx->fuse};
+  if (batch_plan_fusable(flags, cfg)) {
+    // Every launch goes to streams[0], one per group of batches that may run
+    // concurrently (wgcs_batch_plan.h).  The other streams that would have
+    // received a batch are joined before the first launch and forked after the
+    // last, so work queued on them earlier still comes first (an H2D copy
+    // feeding batch j) and work queued later, or a wait on them, still sees
+    // every batch done.
+    const uint32_t used = n_batches < ns ? n_batches : ns;
+    for (uint32_t j = 1; j < used; ++j) {
+      if (st[j] == st[0]) continue;
+      if ((e = hipEventRecord(ctx->join_ev[j], st[j])) != hipSuccess ||
+          (e = hipStreamWaitEvent(st[0], ctx->join_ev[j], 0)) != hipSuccess)
+        return hip_fail(ctx, e, "stream join");
+    }
+    BatchTable tab;
+    uint32_t idx[kBatchGroupMax];
+    for (uint32_t k = 0; k < n_batches;) {
+      k = batch_plan_next(batches, n_batches, k, mode, cfg, &tab, idx);
+      if (tab.count == 1) {  // today's single-batch kernel, unchanged
+        const BatchEntry& b = tab.e[0];
+        e = launch_checksum_batch(mode, flags, b.arena, b.pkts, b.initial, b.n, b.out, st[0], ctx->num_cu, ctx->tune);
+      } else {
+        e = launch_checksum_group(mode, tab, st[0], ctx->tune);
+      }
+      if (e != hipSuccess) return hip_fail(ctx, e, "checksum_batches launch");
+    }
+    bool forked = false;
+    for (uint32_t j = 1; j < used; ++j) {
+      if (st[j] == st[0]) continue;
+      if (!forked && (e = hipEventRecord(ctx->fork_ev, st[0])) != hipSuccess) return hip_fail(ctx, e, "stream fork");
+      forked = true;
+      if ((e = hipStreamWaitEvent(st[j], ctx->fork_ev, 0)) != hipSuccess) return hip_fail(ctx, e, "stream fork");
+    }
+    if (ev_end && (e = hipEventRecord((hipEvent_t)ev_end, st[0])) != hipSuccess) return hip_fail(ctx, e, "ev_end");
+    return WGCS_OK;
+  }
+  // Per-batch launches (WGCS_F_INPLACE, or WGCS_FUSE=0): batch k on stream
+  // k % S.  Batch 0 at once (the first launch is the latency-critical one);
+  // each other stream waits on ev_begin just before its first launch
   for (uint32_t k = 0; k < n_batches; ++k) {
     const uint32_t j = k % ns;
     if (ev_begin && j != 0 && k < ns && st[j] != st[0] &&

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/wgcsum.h"
+#include "wgcs_batch_plan.h"
 #include "wgcs_common.h"
 #include "wgcs_kernels.h"
 
@@ -121,25 +122,26 @@ __device__ __forceinline__ uint4 wave_desc(const uint4* __restrict__ pkts, uint3
 #ifndef WGCS_CS_BLOCK
 #define WGCS_CS_BLOCK 256  // threads per block (A/B builds: 512, 1024)
 #endif
+// The body of one batch: this block is block `blk` of the `nblk` blocks that
+// work on it (the whole grid in the single-batch kernel, the batch's share of
+// the grid in the multi-batch one).
 template <int MODE, int G, int U, bool NT>
-__global__ __launch_bounds__(WGCS_CS_BLOCK) void checksum_batch_kernel(uint8_t* __restrict__ arena,
-                                                             const uint4* __restrict__ pkts,
-                                                             const uint64_t* __restrict__ initial,
-                                                             uint32_t n, void* __restrict__ out,
-                                                             int inplace, uint32_t amask, int xcd) {
+__device__ __forceinline__ void checksum_batch_body(uint8_t* __restrict__ arena, const uint4* __restrict__ pkts,
+                                                    const uint64_t* __restrict__ initial, uint32_t n,
+                                                    void* __restrict__ out, int inplace, uint32_t amask, int xcd,
+                                                    uint32_t blk, const uint32_t nblk) {
   static_assert(G == 16 || G == 32 || G == 64, "group = DPP row, half wave or wave");
   constexpr int PPW = 64 / G;  // packets per wave per step
   const int lane = threadIdx.x & 63;
   const int grp = lane / G;
   const int sub = lane % G;
-  // XCD-aware order (xcd != 0, grid a multiple of 8): blocks are dealt
-  // round-robin over the 8 XCDs, so logical block (b % 8) * (grid / 8) + b / 8
+  // XCD-aware order (xcd != 0, nblk a multiple of 8): blocks are dealt
+  // round-robin over the 8 XCDs, so logical block (b % 8) * (nblk / 8) + b / 8
   // gives each XCD one contiguous eighth of every grid-stride pass -- frames
   // that share a 128-B line at their boundary are fetched through one L2.
-  uint32_t blk = blockIdx.x;
-  if (xcd) blk = (blk & 7u) * (gridDim.x >> 3) + (blk >> 3);
+  if (xcd) blk = (blk & 7u) * (nblk >> 3) + (blk >> 3);
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blk * (blockDim.x >> 6) + (threadIdx.x >> 6)));
-  const uint32_t step = gridDim.x * (blockDim.x >> 6) * PPW;
+  const uint32_t step = nblk * (blockDim.x >> 6) * PPW;
   uint4 dn = wave_desc<PPW>(pkts, wave * PPW, n, grp);
   for (uint32_t base = wave * PPW; base < n; base += step) {  // wave-uniform loop
     const uint32_t p = base + grp;
@@ -293,6 +295,40 @@ __global__ __launch_bounds__(WGCS_CS_BLOCK) void checksum_batch_kernel(uint8_t* 
   }
 }
 
+template <int MODE, int G, int U, bool NT>
+__global__ __launch_bounds__(WGCS_CS_BLOCK) void checksum_batch_kernel(uint8_t* __restrict__ arena,
+                                                             const uint4* __restrict__ pkts,
+                                                             const uint64_t* __restrict__ initial,
+                                                             uint32_t n, void* __restrict__ out,
+                                                             int inplace, uint32_t amask, int xcd) {
+  checksum_batch_body<MODE, G, U, NT>(arena, pkts, initial, n, out, inplace, amask, xcd, blockIdx.x, gridDim.x);
+}
+
+// The multi-batch form (wgcs_batch_plan.h): one launch walks the batches of a
+// group in call order, batch e on blocks [first[e], first[e] + blocks).  The
+// table lives in the kernel-argument segment and the block index is
+// wave-uniform, so the lookup runs on the scalar path: the 32 prefix words in
+// two wide loads and a branch-free count (or one shift when every batch has
+// the same power-of-two block count), then the entry as one more scalar load.
+// Every first[e] is a multiple of 8, so a block's XCD (blockIdx % 8) is the
+// same inside its batch as in the grid, and the grid stride stays per batch.
+// Never in place: such calls keep their per-batch launches.
+template <int MODE, int G, int U, bool NT>
+__global__ __launch_bounds__(WGCS_CS_BLOCK) void checksum_batch_kernel(const BatchTable t, uint32_t amask, int xcd) {
+  const uint32_t bi = blockIdx.x;
+  uint32_t e;
+  if (t.same_shift != kBatchNoEntry) {
+    e = bi >> t.same_shift;
+  } else {
+    e = 0;  // first[] ascends (kBatchNoEntry behind the last entry): the last entry that starts at or below bi
+#pragma unroll
+    for (uint32_t k = 1; k < kBatchGroupMax; ++k) e = bi >= t.first[k] ? k : e;
+  }
+  const BatchEntry& b = t.e[e];
+  checksum_batch_body<MODE, G, U, NT>(b.arena, reinterpret_cast<const uint4*>(b.pkts), b.initial, b.n, b.out, 0, amask,
+                                      xcd, bi - b.first, b.blocks);
+}
+
 template <int MODE>
 static hipError_t launch_mode(uint8_t* arena, const wgcs_pkt* pkts, const uint64_t* init, uint32_t n, void* out,
                               int inplace, hipStream_t s, int num_cu, const LaunchTuning& t) {
@@ -328,6 +364,55 @@ static hipError_t launch_mode(uint8_t* arena, const wgcs_pkt* pkts, const uint64
   }
 #undef WGCS_LAUNCH
   return hipGetLastError();
+}
+
+template <int MODE>
+static hipError_t launch_group_mode(const BatchTable& tab, hipStream_t s, const LaunchTuning& t) {
+  const uint32_t amask = (uint32_t)(t.align >= 16 ? t.align : 16) - 1u;
+  const int xcd = t.xcd ? 1 : 0;  // every batch's block count is a multiple of 8
+#define WGCS_LAUNCH(G, U)                                                                                          \
+  do {                                                                                                            \
+    if (t.nt)                                                                                                     \
+      hipLaunchKernelGGL((checksum_batch_kernel<MODE, G, U, true>), dim3(tab.total), dim3(WGCS_CS_BLOCK), 0, s, tab, \
+                         amask, xcd);                                                                             \
+    else                                                                                                          \
+      hipLaunchKernelGGL((checksum_batch_kernel<MODE, G, U, false>), dim3(tab.total), dim3(WGCS_CS_BLOCK), 0, s, tab, \
+                         amask, xcd);                                                                             \
+  } while (0)
+  if (t.lanes_per_pkt == 64) {
+    if (t.unroll >= 4) WGCS_LAUNCH(64, 4);
+    else WGCS_LAUNCH(64, 2);
+  } else if (t.lanes_per_pkt == 32) {
+    if (t.unroll >= 6) WGCS_LAUNCH(32, 6);
+    else if (t.unroll >= 4) WGCS_LAUNCH(32, 4);
+    else WGCS_LAUNCH(32, 3);
+  } else {
+    if (t.unroll >= 8) WGCS_LAUNCH(16, 8);
+    else if (t.unroll >= 6) WGCS_LAUNCH(16, 6);
+    else WGCS_LAUNCH(16, 4);
+  }
+#undef WGCS_LAUNCH
+  return hipGetLastError();
+}
+
+int checksum_pkts_per_block(const LaunchTuning& t) { return (64 / t.lanes_per_pkt) * (WGCS_CS_BLOCK / 64); }
+
+hipError_t launch_checksum_group(int mode, const BatchTable& tab, hipStream_t s, const LaunchTuning& tune) {
+  if (tab.count == 0 || tab.total == 0) return hipSuccess;
+  switch (mode) {
+    case WGCS_MODE_FOLD:
+      return launch_group_mode<WGCS_MODE_FOLD>(tab, s, tune);
+    case WGCS_MODE_L4_FILL:
+      return launch_group_mode<WGCS_MODE_L4_FILL>(tab, s, tune);
+    case WGCS_MODE_VALIDATE:
+      return launch_group_mode<WGCS_MODE_VALIDATE>(tab, s, tune);
+    case WGCS_MODE_PARTIAL:
+      return launch_group_mode<WGCS_MODE_PARTIAL>(tab, s, tune);
+    case WGCS_MODE_IP4HDR:
+      return launch_group_mode<WGCS_MODE_IP4HDR>(tab, s, tune);
+    default:
+      return hipErrorInvalidValue;
+  }
 }
 
 hipError_t launch_checksum_batch(int mode, unsigned flags, uint8_t* arena, const wgcs_pkt* pkts,

@@ -67,6 +67,9 @@ struct wgcs_ctx {
   wgcs::HostBuf h_stage, h_meta, h_out;
   // stream-join events of wgcs_checksum_batches (timing disabled; [1, 16) made by wgcs_init)
   hipEvent_t join_ev[WGCS_MAX_BATCH_STREAMS] = {};
+  // recorded on streams[0] behind the last launch of a fused call; the other listed streams wait on it
+  hipEvent_t fork_ev = nullptr;
+  bool fuse = true;  // WGCS_FUSE: wgcs_checksum_batches launches groups of batches (wgcs_batch_plan.h)
   // wgcs_host_alloc allocations (device-readable pinned memory): [start, end),
   // the live write stagers, whose zero-copy pushes point into them, and the
   // live read stagers (wgcs_destroy refuses while any stager is alive).  Lock

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/wgcsum.h"
+#include "wgcs_batch_plan.h"
 #include "wgcs_host.h"
 
 namespace wgcs {
@@ -12,6 +13,10 @@ namespace wgcs {
 hipError_t launch_checksum_batch(int mode, unsigned flags, uint8_t* arena, const wgcs_pkt* pkts,
                                  const uint64_t* init, uint32_t n, void* out, hipStream_t s, int num_cu,
                                  const LaunchTuning& tune);
+// One launch for a group of batches (wgcs_batch_plan.h; never in place), and
+// the packets one block covers per grid-stride step, which the plan needs.
+hipError_t launch_checksum_group(int mode, const BatchTable& tab, hipStream_t s, const LaunchTuning& tune);
+int checksum_pkts_per_block(const LaunchTuning& tune);
 
 // the resident per-call ring (ring_kernels.hip): nb workgroups serve the
 // requests of ctl (coherent pinned host memory) until its stop word or
