@@ -45,10 +45,12 @@
  *   wgcs_handshake_screen_batch  CheckMAC1, CheckMAC2 and the cookie reply at the top of
  *                             RoutineHandshake                     device/receive.go:270-287
  *   wgcs_x25519 / _batch      curve25519.X25519                    device/noise_helpers.go:93-105
- *   wgcs_noise_* / wgcs_peer_keys_*  the stateless part of the Noise handshake's first message
- *                                                                  device/noise.go:344-457
+ *   wgcs_noise_* / wgcs_peer_keys_*  the stateless parts of the Noise handshake's two messages
+ *                                                                  device/noise.go:344-457, :494-655
  *   wgcs_handshake_consume_batch  ConsumeMessageInitiation up to its replay / flood check
  *                                                                  device/noise.go:405-457
+ *   wgcs_handshake_respond_batch  CreateMessageResponse, AddMACs and the responder's session keys
+ *                                                                  device/send.go:130-169
  *   wgcs_write_build_batch    one Tun.Write per receive batch and peer, with the peer's
  *                             bookkeeping (_host: on host arrays) device/receive.go:178-228, :398-504
  *   wgcs_stager_*             Tun.Read batch staging              tun/tun.go:477-508
@@ -967,12 +969,20 @@ int wgcs_handshake_screen_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgc
  * compressions, two ChaCha20-Poly1305 opens and a peer lookup by public key.
  * Everything up to the replay / flood check (:458) is stateless and per
  * message -- no clock, no randomness, no per-peer lock -- and runs here over
- * the batch where it landed.  The rest stays with the host: the comparison
- * with lastTimestamp, the HandshakeInitationRate rule and the handshake-state
- * update (:458-491), for which a row of wgcs_hs_init holds what they need;
- * and CreateMessageResponse / ConsumeMessageResponse, which go through a
- * per-handshake ephemeral private key.  Nothing here draws randomness or reads
- * a clock. */
+ * the batch where it landed.  The comparison with lastTimestamp, the
+ * HandshakeInitationRate rule and the handshake-state update (:458-491) stay
+ * with the host, for which a row of wgcs_hs_init holds what they need.  For
+ * every initiation the host accepts, SendHandshakeResponse (send.go:130-169)
+ * then costs three more scalar multiplications, a KDF3, an empty seal, AddMACs
+ * and the key derivation of BeginSymmetricSession: that runs here as well,
+ * over one descriptor per accepted initiation, and leaves the 92-byte response
+ * and the two transport keys in device memory (wgcs_handshake_respond_batch
+ * below).  Its randomness and its session index are the caller's: the
+ * ephemeral private key (newPrivateKey) and the index (sessions.NewIndex, a
+ * host map) are fields of the descriptor.  What stays with the host is that
+ * index allocation, keypair rotation, the timers, and ConsumeMessageResponse
+ * as a batch (the initiator's side exists as a host function).  Nothing here
+ * draws randomness or reads a clock. */
 
 /* curve25519.X25519 (RFC 7748 section 5; noise_helpers.go:93-105): the scalar is
  * clamped inside, bit 255 of the point is ignored, a u in [p, 2^255) is
@@ -1064,6 +1074,90 @@ int wgcs_handshake_consume_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wg
                                  const int32_t *d_type, const int32_t *d_gate, uint32_t n,
                                  const wgcs_noise_responder *d_responder, const wgcs_peer_key *d_table,
                                  uint32_t n_peers, int32_t *d_verdict, wgcs_hs_init *d_out, void *stream);
+
+/* ---- the handshake response (device/noise.go:494-546, :573-604, :636-655,
+ * device/cookie.go:287-314, device/send.go:130-169) ---- */
+
+#define WGCS_HS_RESPONDED 4 /* the response is built and both session keys are in place */
+
+/* The responder's side on the host, for one consumed initiation: the work of
+ * CreateMessageResponse (noise.go:494-546), of AddMACs under the key
+ * BLAKE2s-256("mac1----" | remote_static), and of the responder's
+ * BeginSymmetricSession (KDF2(&decrypt, &encrypt, chainKey, nil), :646-651).
+ * init is a WGCS_HS_CONSUMED row: its hash, chain_key, ephemeral and sender
+ * are read.  The ephemeral private key and local_index (msg.Sender) are the
+ * caller's newPrivateKey() and sessions.NewIndex; preshared_key NULL is the
+ * all-zero key of a peer without one; cookie (16 bytes) NULL leaves MAC2 zero.
+ * msg receives the 92 bytes LE32 2 | LE32 local_index | LE32 init->sender |
+ * ephemeral | empty tag | MAC1 | MAC2; send_key (encrypt) and recv_key
+ * (decrypt) are optional.  WGCS_ERR_LOW_ORDER where one of the three shared
+ * secrets is zero (:520-528): msg and the keys given are then zeroed.
+ * INVALID_ARG for a NULL init, remote_static, ephemeral_private or msg. */
+int wgcs_noise_create_response(const wgcs_hs_init *init, const uint8_t remote_static[32],
+                               const uint8_t preshared_key[32], const uint8_t ephemeral_private[32],
+                               uint32_t local_index, const uint8_t cookie[16], uint8_t msg[92], uint8_t send_key[32],
+                               uint8_t recv_key[32]);
+/* The initiator's side, ConsumeMessageResponse (noise.go:548-620) with its
+ * BeginSymmetricSession (KDF2(&encrypt, &decrypt, chainKey, nil), :638-643):
+ * under the static private key, the hash, chaining key and ephemeral private
+ * key kept from wgcs_noise_create_initiation, and the preshared key (NULL: all
+ * zero).  local_index is the index that handshake is registered under, the
+ * sender of its initiation: sessions.Get(msg.Receiver) must find it.  MACs are
+ * the screen's and are not looked at.  Host only; there is no batch of it.
+ *   len != 92, LE32 msg[0:4] != 2, LE32 msg[8:12] != local_index,
+ *   or a NULL static_private, hash, chain_key, ephemeral_private or msg   WGCS_ERR_INVALID_ARG
+ *   a shared secret with msg[12:44] is all zero                           WGCS_ERR_LOW_ORDER   :575-584
+ *   the empty text msg[44:60] does not open                               WGCS_ERR_AUTH        :599-603
+ *   otherwise 0, *sender = LE32 msg[4:8] (hs.remoteIndex), send_key = encrypt, recv_key = decrypt
+ * The three outputs are optional; a failure zeroes the keys given and leaves *sender. */
+int wgcs_noise_consume_response(const uint8_t static_private[32], const uint8_t hash[32], const uint8_t chain_key[32],
+                                const uint8_t ephemeral_private[32], const uint8_t preshared_key[32],
+                                uint32_t local_index, const uint8_t *msg, size_t len, uint32_t *sender,
+                                uint8_t send_key[32], uint8_t recv_key[32]);
+
+typedef struct wgcs_hs_resp {    /* 80 B, 4-byte aligned: one response to build */
+  uint32_t init_row;             /* row of d_init (and of d_gate) */
+  uint32_t peer_row;             /* row of d_table: remote static; row of d_psk */
+  uint32_t local_index;          /* msg.Sender: the caller's sessions.NewIndex */
+  uint32_t send_key, recv_key;   /* rows of d_keys that receive encrypt / decrypt */
+  uint32_t flags;                /* bit 0: cookie[] is valid, write MAC2 */
+  uint32_t pad[2];
+  uint8_t ephemeral_private[32]; /* the caller's newPrivateKey() */
+  uint8_t cookie[16];
+} wgcs_hs_resp;
+#define WGCS_HS_RESP_COOKIE 0x1u
+
+/* wgcs_noise_create_response over n descriptors, one lane each: an ordinary
+ * launch, asynchronous on stream (NULL: the context's), n <= 2^28, n == 0 a
+ * no-op.  The host's stateful tail (noise.go:458-491) reads the rows of
+ * wgcs_handshake_consume_batch back as before and builds one descriptor per
+ * initiation it accepts, so the launch is dense.  d_init and d_gate are that
+ * call's d_out and d_verdict (d_gate may be NULL: every descriptor is taken);
+ * d_table is its peer table, whose row peer_row gives the remote static key;
+ * d_psk holds one 32-byte preshared key per table row, or is NULL where no
+ * peer has one.  Descriptor j, in this order:
+ *   init_row >= n_init, peer_row >= n_peers, send_key or     d_status[j] = WGCS_ERR_INVALID_ARG; nothing else
+ *   recv_key >= n_keys, or send_key == recv_key               written or read
+ *   d_gate given and d_gate[init_row] != WGCS_HS_CONSUMED     WGCS_HS_NONE; nothing else written
+ *   d_init[init_row].peer != d_table[peer_row].peer           WGCS_ERR_NO_PEER; nothing else written
+ *   a zero shared secret                          :520-528    WGCS_ERR_LOW_ORDER; the 96 bytes at d_msgs + 96 * j
+ *                                                             zeroed, d_keys untouched
+ *   otherwise                                                 WGCS_HS_RESPONDED
+ * For WGCS_HS_RESPONDED the 92 bytes at d_msgs + 96 * j are the response, MACs
+ * included (MAC2 zero without the cookie flag), and the 4 bytes after them are
+ * zero; d_keys[send_key] = {encrypt, remote_index = d_init[init_row].sender,
+ * pad 0} is ready for wgcs_aead_seal_batch and d_keys[recv_key] = {decrypt,
+ * remote_index 0, pad 0} for wgcs_aead_open_batch in the next launch on the
+ * stream: no key crosses to the host.  A descriptor that fails writes no key
+ * material anywhere.  Two descriptors that name one key row are the caller's
+ * error, and which of them wins is unspecified.  d_msgs rows are read back by
+ * the lane that wrote them (the MACs).  Everything is 4-byte aligned.
+ * d_resp holds the ephemeral private keys for as long as it lives, and d_psk
+ * the preshared keys: clear them as the reference clears hs.localEphemeral. */
+int wgcs_handshake_respond_batch(wgcs_ctx *ctx, const wgcs_hs_resp *d_resp, uint32_t n, const wgcs_hs_init *d_init,
+                                 const int32_t *d_gate, uint32_t n_init, const wgcs_peer_key *d_table,
+                                 const uint8_t *d_psk, uint32_t n_peers, wgcs_aead_key *d_keys, uint32_t n_keys,
+                                 uint8_t *d_msgs, int32_t *d_status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,8 @@ PEER_NONE = 0xFFFFFFFF  # Router.Find's nil
 REJECT_AFTER_MESSAGES = 0xFFFFFFFFFFFFDFFF  # constants.go:14
 HS_NONE, HS_PASS, HS_COOKIE = 0, 1, 2  # wgcs_handshake_screen_batch's verdicts
 HS_CONSUMED = 3  # wgcs_handshake_consume_batch's
+HS_RESPONDED = 4  # wgcs_handshake_respond_batch's
+HS_RESP_COOKIE = 0x1  # wgcs_hs_resp.flags: cookie[] is valid
 PEER_RUNNING = 0x1  # wgcs_peer_key.flags: peer.isRunning
 GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
 
@@ -209,6 +211,9 @@ def load() -> C.CDLL:
         "wgcs_noise_create_initiation": ([vp, vp, vp, vp, u32, vp, vp, vp], i32),
         "wgcs_x25519_batch": ([vp, vp, vp, u32, vp, vp, vp], i32),
         "wgcs_handshake_consume_batch": ([vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp], i32),
+        "wgcs_noise_create_response": ([vp, vp, vp, vp, u32, vp, vp, vp, vp], i32),
+        "wgcs_noise_consume_response": ([vp, vp, vp, vp, vp, u32, vp, sz, C.POINTER(u32), vp, vp], i32),
+        "wgcs_handshake_respond_batch": ([vp, vp, u32, vp, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

@@ -1,13 +1,17 @@
-// noise.cpp -- the host functions of the handshake consume step (include/wgcsum.h),
-// no context and no device:
+// noise.cpp -- the host functions of the handshake's consume and response steps
+// (include/wgcsum.h), no context and no device:
 //   wgcs_x25519                      curve25519.X25519              device/noise_helpers.go:93-105
 //   wgcs_noise_responder_init        d.keys and the first mixHash   device/noise.go:91-94, :415
 //   wgcs_peer_keys_build / _find     GetPeer and precomputedSharedSecret   :305, :432
 //   wgcs_noise_consume_initiation    ConsumeMessageInitiation       :405-457
 //   wgcs_noise_create_initiation     CreateMessageInitiation        :344-403
+//   wgcs_noise_create_response       CreateMessageResponse, AddMACs and the responder's keys
+//                                                                   :494-546, :646-651, cookie.go:287-314
+//   wgcs_noise_consume_response      ConsumeMessageResponse and the initiator's keys   :548-620, :638-643
 // They run the scalar code of wgcs_x25519.h and wgcs_noise.h, the code the
-// lanes of noise_kernels.hip run.  Plain C++: a host test program
-// (tests/noise_host/noise_host.cpp) links this file as it is.
+// lanes of noise_kernels.hip run.  Plain C++: the host test programs
+// (tests/noise_host/noise_host.cpp, tests/noise_resp_host/noise_resp_host.cpp)
+// link this file as it is.
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>  // the library's build compiles every file as HIP: WGCS_HD's qualifiers
 #endif
@@ -161,6 +165,54 @@ int wgcs_noise_create_initiation(const uint8_t static_private[32], const uint8_t
   if (hash) bytes_of(h, 8, hash);
   if (chain_key) bytes_of(c, 8, chain_key);
   return WGCS_OK;
+}
+
+int wgcs_noise_create_response(const wgcs_hs_init* init, const uint8_t remote_static[32],
+                               const uint8_t preshared_key[32], const uint8_t ephemeral_private[32],
+                               uint32_t local_index, const uint8_t cookie[16], uint8_t msg[92], uint8_t send_key[32],
+                               uint8_t recv_key[32]) {
+  if (!init || !remote_static || !ephemeral_private || !msg) return WGCS_ERR_INVALID_ARG;
+  uint32_t h[8], c[8], reph[8], remote[8], psk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ek[8], ck[4] = {0, 0, 0, 0};
+  uint32_t m[kNoiseResponseBodyWords], send[8], recv[8], mac1_key[8];
+  words_of(init->hash, 8, h);
+  words_of(init->chain_key, 8, c);
+  words_of(init->ephemeral, 8, reph);
+  words_of(remote_static, 8, remote);
+  words_of(ephemeral_private, 8, ek);
+  if (preshared_key) words_of(preshared_key, 8, psk);
+  if (cookie) words_of(cookie, 4, ck);
+  const int rc = noise_create_response(h, c, reph, remote, psk, ek, local_index, init->sender, m, send, recv);
+  if (send_key) bytes_of(send, 8, send_key);  // zero where rc is not WGCS_OK
+  if (recv_key) bytes_of(recv, 8, recv_key);
+  if (rc != WGCS_OK) {
+    memset(msg, 0, kNoiseResponseSize);
+    return rc;
+  }
+  noise_mac1_key(remote, mac1_key);
+  noise_write_response(msg, m, mac1_key, cookie != nullptr, ck);
+  return WGCS_OK;
+}
+
+int wgcs_noise_consume_response(const uint8_t static_private[32], const uint8_t hash[32], const uint8_t chain_key[32],
+                                const uint8_t ephemeral_private[32], const uint8_t preshared_key[32],
+                                uint32_t local_index, const uint8_t* msg, size_t len, uint32_t* sender,
+                                uint8_t send_key[32], uint8_t recv_key[32]) {
+  uint32_t sk[8], h[8], c[8], ek[8], psk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m[kNoiseResponseBodyWords];
+  uint32_t send[8] = {0, 0, 0, 0, 0, 0, 0, 0}, recv[8] = {0, 0, 0, 0, 0, 0, 0, 0}, from = 0;
+  int rc = WGCS_ERR_INVALID_ARG;
+  if (static_private && hash && chain_key && ephemeral_private && msg && len == kNoiseResponseSize) {
+    words_of(static_private, 8, sk);
+    words_of(hash, 8, h);
+    words_of(chain_key, 8, c);
+    words_of(ephemeral_private, 8, ek);
+    if (preshared_key) words_of(preshared_key, 8, psk);
+    words_of(msg, kNoiseResponseBodyWords, m);
+    rc = noise_consume_response(sk, h, c, ek, psk, local_index, m, &from, send, recv);
+  }
+  if (send_key) bytes_of(send, 8, send_key);
+  if (recv_key) bytes_of(recv, 8, recv_key);
+  if (rc == WGCS_OK && sender) *sender = from;
+  return rc;
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // noise_api.cpp -- C ABI of the device-resident X25519 and handshake consume (include/wgcsum.h):
 //   wgcs_x25519_batch               curve25519.X25519, one per row     device/noise_helpers.go:93-105
 //   wgcs_handshake_consume_batch    ConsumeMessageInitiation to :457   device/noise.go:405-457
+//   wgcs_handshake_respond_batch    CreateMessageResponse, AddMACs, the responder's keys   :494-546, :646-651
 // They run in noise_kernels.hip; the responder, the peer table and the rows
 // are the caller's device memory.  The host functions of the same section are
 // in noise.cpp.
@@ -56,6 +57,26 @@ int wgcs_handshake_consume_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const wg
   const hipError_t e = launch_hs_consume(d_arena, d_pkts, d_type, d_gate, n, d_responder, d_table, n_peers, d_verdict,
                                          d_out, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "handshake_consume launch");
+}
+
+int wgcs_handshake_respond_batch(wgcs_ctx* ctx, const wgcs_hs_resp* d_resp, uint32_t n, const wgcs_hs_init* d_init,
+                                 const int32_t* d_gate, uint32_t n_init, const wgcs_peer_key* d_table,
+                                 const uint8_t* d_psk, uint32_t n_peers, wgcs_aead_key* d_keys, uint32_t n_keys,
+                                 uint8_t* d_msgs, int32_t* d_status, void* stream) {
+  if (!ctx) return WGCS_ERR_INVALID_ARG;
+  if (n == 0) return WGCS_OK;
+  if (!d_resp || !d_msgs || !d_status || (n_init && !d_init) || (n_peers && !d_table) || (n_keys && !d_keys))
+    return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
+  if (n > kMaxBatch || ((uintptr_t)d_resp & 3) || ((uintptr_t)d_init & 3) || ((uintptr_t)d_gate & 3) ||
+      ((uintptr_t)d_table & 3) || ((uintptr_t)d_psk & 3) || ((uintptr_t)d_keys & 3) || ((uintptr_t)d_msgs & 3) ||
+      ((uintptr_t)d_status & 3))
+    return set_err(ctx, WGCS_ERR_INVALID_ARG,
+                   "n <= 2^28, 4-byte aligned d_resp / d_init / d_gate / d_table / d_psk / d_keys / d_msgs / d_status");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  hipSetDevice(ctx->device);
+  const hipError_t e = launch_hs_respond(d_resp, n, d_init, d_gate, n_init, d_table, d_psk, n_peers, d_keys, n_keys,
+                                         d_msgs, d_status, stream ? (hipStream_t)stream : ctx->stream);
+  return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "handshake_respond launch");
 }
 
 }  // extern "C"

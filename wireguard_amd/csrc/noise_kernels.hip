@@ -3,6 +3,8 @@
 //   x25519_kernel       curve25519.X25519, one per row          device/noise_helpers.go:93-105
 //   hs_consume_kernel   ConsumeMessageInitiation up to the replay / flood check
 //                                                                device/noise.go:405-457
+//   hs_respond_kernel   CreateMessageResponse, AddMACs and the responder's session keys
+//                                                                device/noise.go:494-546, :646-651
 // One lane per row, as the handshake screen: a lane runs the Montgomery ladder
 // of wgcs_x25519.h -- 255 steps of five multiplications, four squarings and
 // one multiplication by a24, then the inversion, some 2,800 field
@@ -91,7 +93,92 @@ __global__ __launch_bounds__(kThreads) void hs_consume_kernel(const uint8_t* __r
   for (uint32_t i = 0; i < kHsInitWords; ++i) row[i] = o[i];
 }
 
+// The words of wgcs_hs_resp: 0 init_row | 1 peer_row | 2 local_index | 3 send_key | 4 recv_key | 5 flags |
+// 6..7 pad | 8..15 ephemeral private | 16..19 cookie.
+constexpr uint32_t kHsRespWords = sizeof(wgcs_hs_resp) / 4;
+constexpr uint32_t kPeerKeyWords = sizeof(wgcs_peer_key) / 4;  // 0..7 public key | 8..15 shared | 16 peer | 17 flags
+constexpr uint32_t kAeadKeyWords = sizeof(wgcs_aead_key) / 4;  // 0..7 key | 8 remote_index | 9..11 pad
+constexpr uint32_t kRespPitchWords = 24;                       // a row of d_msgs: the 92 bytes and 4 of zero
+
+// One descriptor per lane: noise_create_response, AddMACs and both key rows.  The three
+// scalar multiplications share one ladder inside noise_create_response, so the kernel holds
+// the registers of hs_consume_kernel and not three times its code.  Every load and store is
+// an aligned dword; the lane reads its own d_msgs row back for the two MACs.
+__global__ __launch_bounds__(kThreads) void hs_respond_kernel(const uint32_t* __restrict__ resp, uint32_t n,
+                                                              const uint32_t* __restrict__ init,
+                                                              const int32_t* __restrict__ gate, uint32_t n_init,
+                                                              const uint32_t* __restrict__ table,
+                                                              const uint32_t* __restrict__ psk_table, uint32_t n_peers,
+                                                              uint32_t* keys, uint32_t n_keys, uint8_t* msgs,
+                                                              int32_t* __restrict__ status) {
+  const uint32_t q = blockIdx.x * kThreads + threadIdx.x;
+  if (q >= n) return;
+  const uint32_t* const d = resp + kHsRespWords * (uint64_t)q;
+  const uint32_t init_row = d[0], peer_row = d[1], local_index = d[2], send_row = d[3], recv_row = d[4], flags = d[5];
+  if (init_row >= n_init || peer_row >= n_peers || send_row >= n_keys || recv_row >= n_keys || send_row == recv_row) {
+    status[q] = WGCS_ERR_INVALID_ARG;
+    return;
+  }
+  if (gate && gate[init_row] != WGCS_HS_CONSUMED) {  // the host's timestamp or flood rule masked it
+    status[q] = WGCS_HS_NONE;
+    return;
+  }
+  const uint32_t* const in = init + kHsInitWords * (uint64_t)init_row;
+  const uint32_t* const peer = table + kPeerKeyWords * (uint64_t)peer_row;
+  if (in[0] != peer[16]) {  // not the peer this initiation authenticated as
+    status[q] = WGCS_ERR_NO_PEER;
+    return;
+  }
+  uint32_t hash0[8], chain0[8], remote_eph[8], remote_static[8], psk[8], eph_priv[8], cookie[4];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    hash0[i] = in[8 + i];
+    chain0[i] = in[16 + i];
+    remote_eph[i] = in[24 + i];
+    remote_static[i] = peer[i];
+    psk[i] = psk_table ? psk_table[8 * (uint64_t)peer_row + i] : 0u;
+    eph_priv[i] = d[8 + i];
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) cookie[i] = d[16 + i];
+  uint32_t m[kNoiseResponseBodyWords], send_key[8], recv_key[8];
+  const int rc = noise_create_response(hash0, chain0, remote_eph, remote_static, psk, eph_priv, local_index, in[1], m,
+                                       send_key, recv_key);
+  uint8_t* const row = msgs + 4 * kRespPitchWords * (uint64_t)q;
+  if (rc != WGCS_OK) {  // a zero shared secret: no key row is touched
+#pragma unroll
+    for (uint32_t i = 0; i < kRespPitchWords; ++i) ((uint32_t*)row)[i] = 0;
+    status[q] = rc;
+    return;
+  }
+  uint32_t mac1_key[8];
+  noise_mac1_key(remote_static, mac1_key);
+  noise_write_response(row, m, mac1_key, (flags & WGCS_HS_RESP_COOKIE) != 0, cookie);
+  ((uint32_t*)row)[kRespPitchWords - 1] = 0;
+  uint32_t* const ks = keys + kAeadKeyWords * (uint64_t)send_row;
+  uint32_t* const kr = keys + kAeadKeyWords * (uint64_t)recv_row;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    ks[i] = send_key[i];
+    kr[i] = recv_key[i];
+  }
+  ks[8] = in[1];  // the receiver index of every transport message sealed under this key
+  kr[8] = 0;
+#pragma unroll
+  for (int i = 9; i < 12; ++i) ks[i] = kr[i] = 0;
+  status[q] = WGCS_HS_RESPONDED;
+}
+
 }  // namespace
+
+hipError_t launch_hs_respond(const wgcs_hs_resp* resp, uint32_t n, const wgcs_hs_init* init, const int32_t* gate,
+                             uint32_t n_init, const wgcs_peer_key* table, const uint8_t* psk, uint32_t n_peers,
+                             wgcs_aead_key* keys, uint32_t n_keys, uint8_t* msgs, int32_t* status, hipStream_t s) {
+  hipLaunchKernelGGL(hs_respond_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s,
+                     (const uint32_t*)resp, n, (const uint32_t*)init, gate, n_init, (const uint32_t*)table,
+                     (const uint32_t*)psk, n_peers, (uint32_t*)keys, n_keys, msgs, status);
+  return hipGetLastError();
+}
 
 hipError_t launch_x25519(const uint8_t* scalars, const uint8_t* points, uint32_t n, uint8_t* out, int32_t* status,
                          hipStream_t s) {

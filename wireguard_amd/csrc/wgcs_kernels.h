@@ -102,5 +102,9 @@ hipError_t launch_hs_consume(const uint8_t* arena, const wgcs_aead_pkt* pkts, co
                              const int32_t* gate, uint32_t n, const wgcs_noise_responder* responder,
                              const wgcs_peer_key* table, uint32_t n_peers, int32_t* verdict, wgcs_hs_init* out,
                              hipStream_t s);
+// the response to n accepted initiations, one lane per descriptor; gate and psk may be NULL
+hipError_t launch_hs_respond(const wgcs_hs_resp* resp, uint32_t n, const wgcs_hs_init* init, const int32_t* gate,
+                             uint32_t n_init, const wgcs_peer_key* table, const uint8_t* psk, uint32_t n_peers,
+                             wgcs_aead_key* keys, uint32_t n_keys, uint8_t* msgs, int32_t* status, hipStream_t s);
 
 }  // namespace wgcs

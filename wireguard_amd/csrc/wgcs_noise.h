@@ -1,8 +1,10 @@
-// wgcs_noise.h -- the scalar steps of the reference's Noise_IKpsk2 handshake up
-// to the consumption of an initiation (device/noise.go:91-94, :324-457,
-// device/noise_helpers.go:18-58), shared by hs_consume_kernel
-// (noise_kernels.hip), the host functions of noise.cpp and
-// tests/noise_host/noise_host.cpp.
+// wgcs_noise.h -- the scalar steps of the reference's Noise_IKpsk2 handshake:
+// the initiation and its consumption (device/noise.go:91-94, :324-457,
+// device/noise_helpers.go:18-58), the response, its consumption and the
+// session keys of both sides (noise.go:494-546, :573-604, :636-655), shared by
+// hs_consume_kernel and hs_respond_kernel (noise_kernels.hip), the host
+// functions of noise.cpp and the host test programs
+// tests/noise_host/noise_host.cpp and tests/noise_resp_host/noise_resp_host.cpp.
 //
 // Everything is little-endian words in registers: a hash, a chaining key, a
 // key, a public key and a shared secret are 8 words, a message is its 37.
@@ -21,12 +23,16 @@
 // An initiation (MessageInitiation, noise.go:100-125) in words:
 //   0 type | 1 sender | 2..9 ephemeral | 10..17 static ct | 18..21 its tag |
 //   22..24 timestamp ct | 25..28 its tag | 29..32 MAC1 | 33..36 MAC2
+// A response (MessageResponse, noise.go:159-174) in words:
+//   0 type | 1 sender | 2 receiver | 3..10 ephemeral | 11..14 the empty text's tag |
+//   15..18 MAC1 | 19..22 MAC2
 #pragma once
 
 #include <stdint.h>
 
 #include "../../include/wgcsum.h"
 #include "wgcs_blake2s.h"
+#include "wgcs_cookie.h"
 #include "wgcs_x25519.h"
 #include "wgcs_xchacha.h"
 
@@ -331,6 +337,164 @@ WGCS_HD int noise_create_initiation(const uint32_t static_priv[8], const uint32_
 #pragma unroll
   for (int i = 0; i < 4; ++i) m[25 + i] = ts_tag[i];
   noise_mix_hash(hash, m + 22, 28);  // :400: m[29..33] are still zero
+  return WGCS_OK;
+}
+
+constexpr uint32_t kNoiseResponseSize = 92;       // MessageResponseSize, noise.go:62
+constexpr uint32_t kNoiseResponseType = 2;        // MessageResponseType
+constexpr uint32_t kNoiseResponseBodyWords = 15;  // everything before MAC1
+
+// CreateMessageResponse (noise.go:494-546) and the responder's half of BeginSymmetricSession
+// (:645-652) for one consumed initiation -- hash0, chain0 and remote_eph are the hash,
+// chain_key and ephemeral of its wgcs_hs_init row, remote_index its sender -- with the
+// caller's ephemeral private key and session index: the 15 words of the message before its
+// MACs, send_key = encrypt and recv_key = decrypt.  psk is all zero where the peer has none.
+// WGCS_ERR_LOW_ORDER where one of the three X25519 results is zero (:520-528; the public key
+// of base point 9 never is, but it runs the one code path); m and both keys are then zero.
+// The three scalar multiplications do not depend on the hashing between them, so they come
+// first and share one ladder: the body of x25519_words exists once in the code.
+WGCS_HD int noise_create_response(const uint32_t hash0[8], const uint32_t chain0[8], const uint32_t remote_eph[8],
+                                  const uint32_t remote_static[8], const uint32_t psk[8], const uint32_t eph_priv[8],
+                                  uint32_t local_index, uint32_t remote_index, uint32_t m[kNoiseResponseBodyWords],
+                                  uint32_t send_key[8], uint32_t recv_key[8]) {
+  uint32_t eph[8], ee[8], es[8];
+  bool ok = true;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int i = 0; i < 3; ++i) {  // the step is the same for every lane: no secret decides it
+    uint32_t point[8], r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) point[j] = i == 0 ? (j == 0 ? 9u : 0u) : i == 1 ? remote_eph[j] : remote_static[j];
+    ok = x25519_words(eph_priv, point, r) && ok;
+    if (i == 0) {  // :517 localEphemeral.publicKey()
+#pragma unroll
+      for (int j = 0; j < 8; ++j) eph[j] = r[j];
+    } else if (i == 1) {  // :520 sharedSecret(hs.remoteEphemeral)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ee[j] = r[j];
+    } else {  // :525 sharedSecret(hs.remoteStatic)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) es[j] = r[j];
+    }
+  }
+#pragma unroll
+  for (uint32_t i = 0; i < kNoiseResponseBodyWords; ++i) m[i] = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) send_key[i] = recv_key[i] = 0;
+  if (!ok) return WGCS_ERR_LOW_ORDER;  // :520-528
+  uint32_t hash[8], chain[8], tau[8], key[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    hash[i] = hash0[i];
+    chain[i] = chain0[i];
+  }
+  m[0] = kNoiseResponseType;  // :509
+  m[1] = local_index;         // :510
+  m[2] = remote_index;        // :511
+#pragma unroll
+  for (int i = 0; i < 8; ++i) m[3 + i] = eph[i];  // :517
+  const uint32_t eph12[12] = {eph[0], eph[1], eph[2], eph[3], eph[4], eph[5], eph[6], eph[7], 0, 0, 0, 0};
+  noise_mix_hash(hash, eph12, 32);  // :518
+  noise_mix_key(chain, eph);        // :519
+  noise_mix_key(chain, ee);         // :524
+  noise_mix_key(chain, es);         // :529
+  // add preshared key
+  uint32_t in[16];
+  noise_pad32(psk, in);
+  noise_kdf3(chain, tau, key, chain, in, 32);  // :533-539
+  const uint32_t tau12[12] = {tau[0], tau[1], tau[2], tau[3], tau[4], tau[5], tau[6], tau[7], 0, 0, 0, 0};
+  noise_mix_hash(hash, tau12, 32);  // :540
+  const uint32_t none[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t ct[8];
+  noise_seal(key, none, 0, hash, ct, m + 11);  // :542
+  // :543 mixes msg.Empty into hs.hash, which nothing reads before BeginSymmetricSession zeroes it (:658)
+  noise_kdf2(recv_key, send_key, chain, none, 0);  // :646-651: KDF2(&decryptKey, &encryptKey, chainKey, nil)
+  return WGCS_OK;
+}
+
+// The key of MAC1 for a message to the holder of the static public key pub:
+// BLAKE2s-256("mac1----" | pub), CookieGenerator.Init (cookie.go:269-275)
+WGCS_HD void noise_mac1_key(const uint32_t pub[8], uint32_t key[8]) {
+  const uint32_t in[32] = {0x3163616Du, 0x2D2D2D2Du, pub[0], pub[1], pub[2], pub[3], pub[4], pub[5], pub[6], pub[7],
+                           0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  noise_hash(in, 40, key);
+}
+
+// n words to p: aligned dword stores on the device, where a row is 4-byte aligned, byte stores on the host
+WGCS_HD void noise_store_words(uint8_t* p, const uint32_t* w, uint32_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t* const d = (uint32_t*)p;
+#pragma unroll
+  for (uint32_t i = 0; i < n; ++i) d[i] = w[i];
+#else
+  for (uint32_t i = 0; i < n; ++i) b2s_store_le32(p + 4 * i, w[i]);
+#endif
+}
+
+// The 92 bytes of a response at msg from the words of noise_create_response, with AddMACs
+// (cookie.go:287-314): MAC1 under mac1_key over the 60 bytes before it, and MAC2 under the
+// cookie over the 76 bytes before it, or zero without one (:307-309).  The MACs are taken over
+// the bytes just stored.
+WGCS_HD void noise_write_response(uint8_t* msg, const uint32_t m[kNoiseResponseBodyWords], const uint32_t mac1_key[8],
+                                  bool has_cookie, const uint32_t cookie[4]) {
+  uint32_t mac[4];
+  noise_store_words(msg, m, kNoiseResponseBodyWords);
+  cookie_mac128(mac1_key, 32, msg, kNoiseResponseSize - 2 * kMacSize, mac);  // :296-300
+  noise_store_words(msg + (kNoiseResponseSize - 2 * kMacSize), mac, 4);
+  if (has_cookie) {
+    const uint32_t key[8] = {cookie[0], cookie[1], cookie[2], cookie[3], 0, 0, 0, 0};
+    cookie_mac128(key, 16, msg, kNoiseResponseSize - kMacSize, mac);  // :309-313
+  } else {
+    mac[0] = mac[1] = mac[2] = mac[3] = 0;
+  }
+  noise_store_words(msg + (kNoiseResponseSize - kMacSize), mac, 4);
+}
+
+// ConsumeMessageResponse (noise.go:548-620) and the initiator's half of BeginSymmetricSession
+// (:637-644) for the words m of a response, under the initiator's static private key, the
+// hash, chaining key and ephemeral private key it kept from CreateMessageInitiation and the
+// preshared key (zero where there is none).  local_index is the index this handshake is
+// registered under: sessions.Get(msg.Receiver) finding another one, or none (:553-557), and a
+// wrong type word (:549-551) are WGCS_ERR_INVALID_ARG.  WGCS_ERR_LOW_ORDER where a shared
+// secret is zero (:575-584), WGCS_ERR_AUTH where the empty text does not open (:600-603);
+// both keys are zero for every failure.  Else WGCS_OK, *sender = msg.Sender (:614),
+// send_key = encrypt and recv_key = decrypt.
+WGCS_HD int noise_consume_response(const uint32_t static_priv[8], const uint32_t hash0[8], const uint32_t chain0[8],
+                                   const uint32_t eph_priv[8], const uint32_t psk[8], uint32_t local_index,
+                                   const uint32_t m[kNoiseResponseBodyWords], uint32_t* sender, uint32_t send_key[8],
+                                   uint32_t recv_key[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) send_key[i] = recv_key[i] = 0;
+  if (m[0] != kNoiseResponseType || m[2] != local_index) return WGCS_ERR_INVALID_ARG;  // :549-557
+  uint32_t hash[8], chain[8], eph[8], shared[8], tau[8], key[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    hash[i] = hash0[i];
+    chain[i] = chain0[i];
+    eph[i] = m[3 + i];
+  }
+  // finish 3-way DH
+  const uint32_t eph12[12] = {eph[0], eph[1], eph[2], eph[3], eph[4], eph[5], eph[6], eph[7], 0, 0, 0, 0};
+  noise_mix_hash(hash, eph12, 32);                                               // :573
+  noise_mix_key(chain, eph);                                                     // :574
+  if (!x25519_words(eph_priv, eph, shared)) return WGCS_ERR_LOW_ORDER;           // :575-578
+  noise_mix_key(chain, shared);                                                  // :579
+  if (!x25519_words(static_priv, eph, shared)) return WGCS_ERR_LOW_ORDER;        // :581-584
+  noise_mix_key(chain, shared);                                                  // :585
+  // add preshared key (psk)
+  uint32_t in[16];
+  noise_pad32(psk, in);
+  noise_kdf3(chain, tau, key, chain, in, 32);  // :590-596
+  const uint32_t tau12[12] = {tau[0], tau[1], tau[2], tau[3], tau[4], tau[5], tau[6], tau[7], 0, 0, 0, 0};
+  noise_mix_hash(hash, tau12, 32);  // :597
+  // authenticate transcript
+  const uint32_t none[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t pt[8];
+  if (!noise_open(key, none, 0, m + 11, hash, pt)) return WGCS_ERR_AUTH;  // :599-603
+  // :604 mixes msg.Empty into the hash, which nothing reads before BeginSymmetricSession zeroes it (:658)
+  *sender = m[1];                                  // :614
+  noise_kdf2(send_key, recv_key, chain, none, 0);  // :638-643: KDF2(&encryptKey, &decryptKey, chainKey, nil)
   return WGCS_OK;
 }
 

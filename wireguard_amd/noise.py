@@ -7,11 +7,15 @@ Names and argument meaning follow the reference:
   peer_keys_build(responder, keys, peers, flags)  the table GetPeer reads, with precomputedSharedSecret, :305, :432
   consume_initiation                              ConsumeMessageInitiation up to the replay / flood check, :405-457
   create_initiation                               CreateMessageInitiation, :344-403
-  x25519_batch / consume_batch                    the same over device-resident rows
+  create_response                                 CreateMessageResponse, AddMACs and the responder's
+                                                  BeginSymmetricSession keys, :494-546, :646-651
+  consume_response                                ConsumeMessageResponse and the initiator's keys, :548-620, :638-643
+  x25519_batch / consume_batch / respond_batch    the same over device-resident rows
 The clock, the randomness and the handshake state are the caller's: the
-ephemeral private key, the timestamp and the sender index are arguments, and
+ephemeral private keys, the timestamp and the session indices are arguments, and
 what follows noise.go:457 -- the comparison with lastTimestamp, the flood rule,
-the state update -- takes a HS_INIT_DTYPE row and stays with the host.
+the state update -- takes a HS_INIT_DTYPE row and stays with the host, which
+then builds one HS_RESP_DTYPE descriptor per initiation it accepts.
 Curve25519, the HMAC / HKDF layer, the AEAD and the kernels live in
 libwgcsum.so (wgcs_x25519.h, wgcs_noise.h, noise_kernels.hip); nothing here
 computes.
@@ -23,9 +27,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import ERR_AUTH, ERR_LOW_ORDER, ERR_NO_PEER, HS_CONSUMED, HS_NONE, HS_PASS, PEER_NONE, PEER_RUNNING
+from ._lib import (ERR_AUTH, ERR_LOW_ORDER, ERR_NO_PEER, HS_CONSUMED, HS_NONE, HS_PASS, HS_RESP_COOKIE, HS_RESPONDED,
+                   PEER_NONE, PEER_RUNNING)
 from .cookie import _fixed, _status
-from .transport import AEAD_PKT_DTYPE, _rows
+from .transport import AEAD_KEY_DTYPE, AEAD_PKT_DTYPE, _rows
 from .tun import _ptr
 
 NOISE_RESPONDER_DTYPE = np.dtype([("private_key", "u1", (32,)), ("hash0", "u1", (32,)),
@@ -34,11 +39,18 @@ PEER_KEY_DTYPE = np.dtype([("public_key", "u1", (32,)), ("shared", "u1", (32,)),
                            ("flags", "<u4")])  # wgcs_peer_key
 HS_INIT_DTYPE = np.dtype([("peer", "<u4"), ("sender", "<u4"), ("timestamp", "u1", (12,)), ("pad", "u1", (12,)),
                           ("hash", "u1", (32,)), ("chain_key", "u1", (32,)), ("ephemeral", "u1", (32,))])  # wgcs_hs_init
+HS_RESP_DTYPE = np.dtype([("init_row", "<u4"), ("peer_row", "<u4"), ("local_index", "<u4"), ("send_key", "<u4"),
+                          ("recv_key", "<u4"), ("flags", "<u4"), ("pad", "<u4", (2,)), ("ephemeral_private", "u1", (32,)),
+                          ("cookie", "u1", (16,))])  # wgcs_hs_resp
+RESPONSE_SIZE, RESPONSE_PITCH = 92, 96  # MessageResponseSize; a row of respond_batch's msgs
 assert NOISE_RESPONDER_DTYPE.itemsize == 96 and PEER_KEY_DTYPE.itemsize == 72 and HS_INIT_DTYPE.itemsize == 128
+assert HS_RESP_DTYPE.itemsize == 80
 
 __all__ = ["NOISE_RESPONDER_DTYPE", "PEER_KEY_DTYPE", "HS_INIT_DTYPE", "x25519", "responder_init", "peer_keys_build",
            "peer_keys_find", "consume_initiation", "create_initiation", "x25519_batch", "consume_batch", "HS_NONE",
-           "HS_PASS", "HS_CONSUMED", "ERR_AUTH", "ERR_LOW_ORDER", "ERR_NO_PEER", "PEER_NONE", "PEER_RUNNING"]
+           "HS_PASS", "HS_CONSUMED", "ERR_AUTH", "ERR_LOW_ORDER", "ERR_NO_PEER", "PEER_NONE", "PEER_RUNNING",
+           "HS_RESP_DTYPE", "RESPONSE_SIZE", "RESPONSE_PITCH", "create_response", "consume_response", "respond_batch",
+           "HS_RESPONDED", "HS_RESP_COOKIE"]
 
 
 def _one(x, dtype: np.dtype, what: str) -> np.ndarray:
@@ -118,6 +130,40 @@ def create_initiation(static_private, remote_static, ephemeral_private, timestam
     return msg.raw, h.raw, ck.raw
 
 
+def create_response(init, remote_static, ephemeral_private, local_index: int, preshared_key=None, cookie=None
+                    ) -> tuple[int, bytes, bytes, bytes]:
+    """(status, the 92-byte response with its MACs, send key, recv key) for one
+    HS_INIT_DTYPE row that consume_initiation returned with HS_CONSUMED: status
+    0, or ERR_LOW_ORDER with all three zeroed.  preshared_key None is the
+    all-zero key; cookie (16 bytes) None leaves MAC2 zero."""
+    row = _one(init, HS_INIT_DTYPE, "HS_INIT_DTYPE")
+    msg, send, recv = C.create_string_buffer(92), C.create_string_buffer(32), C.create_string_buffer(32)
+    rc = _lib.load().wgcs_noise_create_response(
+        row.ctypes.data, _fixed(remote_static, 32, "a public key"),
+        None if preshared_key is None else _fixed(preshared_key, 32, "a preshared key"),
+        _fixed(ephemeral_private, 32, "an ephemeral private key"), local_index & 0xFFFFFFFF,
+        None if cookie is None else _fixed(cookie, 16, "a cookie"), msg, send, recv)
+    if rc != ERR_LOW_ORDER:
+        _status(rc, "wgcs_noise_create_response")
+    return rc, msg.raw, send.raw, recv.raw
+
+
+def consume_response(static_private, hash_, chain_key, ephemeral_private, local_index: int, msg, preshared_key=None
+                     ) -> tuple[int, int | None, bytes, bytes]:
+    """(status, sender index, send key, recv key) on the initiator's side, under
+    what create_initiation returned and the index it was sent with: status 0, or
+    ERR_INVALID_ARG (a length other than 92, a wrong type word, another
+    receiver), ERR_LOW_ORDER or ERR_AUTH with no sender and zero keys."""
+    m = bytes(msg)
+    sender, send, recv = C.c_uint32(0), C.create_string_buffer(32), C.create_string_buffer(32)
+    rc = _lib.load().wgcs_noise_consume_response(
+        _fixed(static_private, 32, "a private key"), _fixed(hash_, 32, "a hash"), _fixed(chain_key, 32, "a chaining key"),
+        _fixed(ephemeral_private, 32, "an ephemeral private key"),
+        None if preshared_key is None else _fixed(preshared_key, 32, "a preshared key"), local_index & 0xFFFFFFFF, m,
+        len(m), C.byref(sender), send, recv)
+    return rc, sender.value if rc == 0 else None, send.raw, recv.raw
+
+
 def x25519_batch(dev, scalars, points, out, status, stream=None, n: int | None = None) -> None:
     """Asynchronous wgcs_x25519_batch over 32-byte rows on the device: out row q
     = X25519(scalars row q, points row q), status[q] (int32) = 0 or ERR_LOW_ORDER."""
@@ -141,3 +187,23 @@ def consume_batch(dev, arena, pkts, types, gate, responder, table, verdict, out,
     dev._check(dev.lib.wgcs_handshake_consume_batch(dev.h, _ptr(arena), _ptr(pkts), _ptr(types), _ptr(gate), n,
                                                     _ptr(responder), _ptr(table) if n_peers else None, n_peers,
                                                     _ptr(verdict), _ptr(out), s))
+
+
+def respond_batch(dev, resp, init, gate, table, psk, keys, msgs, status, stream=None, n: int | None = None,
+                  n_init: int | None = None, n_peers: int | None = None, n_keys: int | None = None) -> None:
+    """Asynchronous wgcs_handshake_respond_batch over HS_RESP_DTYPE descriptors:
+    `init` and `gate` are consume_batch's out and verdict (gate None: every
+    descriptor is taken), `table` its PEER_KEY_DTYPE rows, `psk` 32 bytes per
+    table row or None, `keys` the AEAD_KEY_DTYPE table that seal_batch and
+    open_batch read.  status[j] (int32) = HS_RESPONDED, HS_NONE,
+    ERR_INVALID_ARG, ERR_NO_PEER or ERR_LOW_ORDER, and msgs (RESPONSE_PITCH
+    bytes per descriptor) and keys as the header says.  Everything is on the
+    device."""
+    s = getattr(stream, "cuda_stream", stream)
+    n = _rows(resp, HS_RESP_DTYPE) if n is None else n
+    n_init = (0 if init is None else _rows(init, HS_INIT_DTYPE)) if n_init is None else n_init
+    n_peers = (0 if table is None else _rows(table, PEER_KEY_DTYPE)) if n_peers is None else n_peers
+    n_keys = (0 if keys is None else _rows(keys, AEAD_KEY_DTYPE)) if n_keys is None else n_keys
+    dev._check(dev.lib.wgcs_handshake_respond_batch(dev.h, _ptr(resp), n, _ptr(init) if n_init else None, _ptr(gate),
+                                                    n_init, _ptr(table) if n_peers else None, _ptr(psk), n_peers,
+                                                    _ptr(keys) if n_keys else None, n_keys, _ptr(msgs), _ptr(status), s))
