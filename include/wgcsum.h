@@ -95,7 +95,9 @@ extern "C" {
 #define WGCS_ERR_MAC1 (-21)             /* "Received packet with invalid mac1" receive.go:272-275 */
 #define WGCS_ERR_LOW_ORDER (-22)        /* "bad input point: low order point" curve25519.X25519, noise.go:421-424 */
 #define WGCS_ERR_NO_PEER (-23)          /* GetPeer found none, or it is not running / has no shared secret  noise.go:432-443 */
-#define WGCS_ERR_HIP (-100)           /* HIP runtime error (message: wgcs_last_error) */
+#define WGCS_ERR_NO_HANDSHAKE (-24)    /* sessions.Get(msg.Receiver) finds no handshake, or its state is not
+                                          handshakeInitiationCreated  noise.go:553-557, :566 */
+#define WGCS_ERR_HIP (-100)          /* HIP runtime error (message: wgcs_last_error) */
 #define WGCS_ERR_NOMEM (-101)
 #define WGCS_ERR_NO_DEVICE (-102)
 
@@ -979,10 +981,13 @@ int wgcs_handshake_screen_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgc
  * and the two transport keys in device memory (wgcs_handshake_respond_batch
  * below).  Its randomness and its session index are the caller's: the
  * ephemeral private key (newPrivateKey) and the index (sessions.NewIndex, a
- * host map) are fields of the descriptor.  What stays with the host is that
- * index allocation, keypair rotation, the timers, and ConsumeMessageResponse
- * as a batch (the initiator's side exists as a host function).  Nothing here
- * draws randomness or reads a clock. */
+ * host map) are fields of the descriptor.  The initiator's half --
+ * CreateMessageInitiation and ConsumeMessageResponse with its session keys --
+ * runs here too, joined by a table of handshake states in device memory
+ * (wgcs_handshake_initiate_batch and wgcs_handshake_finish_batch, the last
+ * section).  What stays with the host is index allocation, lastSentHandshake
+ * and the timers, keypair rotation and the consumption of cookie replies.
+ * Nothing here draws randomness or reads a clock. */
 
 /* curve25519.X25519 (RFC 7748 section 5; noise_helpers.go:93-105): the scalar is
  * clamped inside, bit 255 of the point is ignored, a u in [p, 2^255) is
@@ -1103,7 +1108,8 @@ int wgcs_noise_create_response(const wgcs_hs_init *init, const uint8_t remote_st
  * key kept from wgcs_noise_create_initiation, and the preshared key (NULL: all
  * zero).  local_index is the index that handshake is registered under, the
  * sender of its initiation: sessions.Get(msg.Receiver) must find it.  MACs are
- * the screen's and are not looked at.  Host only; there is no batch of it.
+ * the screen's and are not looked at.  One message on the host; the batch over
+ * device-resident states is wgcs_handshake_finish_batch.
  *   len != 92, LE32 msg[0:4] != 2, LE32 msg[8:12] != local_index,
  *   or a NULL static_private, hash, chain_key, ephemeral_private or msg   WGCS_ERR_INVALID_ARG
  *   a shared secret with msg[12:44] is all zero                           WGCS_ERR_LOW_ORDER   :575-584
@@ -1158,6 +1164,135 @@ int wgcs_handshake_respond_batch(wgcs_ctx *ctx, const wgcs_hs_resp *d_resp, uint
                                  const int32_t *d_gate, uint32_t n_init, const wgcs_peer_key *d_table,
                                  const uint8_t *d_psk, uint32_t n_peers, wgcs_aead_key *d_keys, uint32_t n_keys,
                                  uint8_t *d_msgs, int32_t *d_status, void *stream);
+
+/* ---- the handshake initiator (device/noise.go:344-403, :548-620, :636-662,
+ * device/cookie.go:287-314) ----
+ * SendHandshakeInitiation and the receipt of its response over device-resident
+ * batches.  A table of wgcs_hs_state rows in device memory, one per handshake
+ * in flight, joins the two launches: wgcs_handshake_initiate_batch fills a row
+ * and wgcs_handshake_finish_batch consumes it, so neither the ephemeral secret
+ * nor a transport key of the initiator crosses to the host.  The host keeps
+ * what the reference keeps under locks and clocks: sessions.NewIndex,
+ * lastSentHandshake and the timers, keypair rotation, and the consumption of
+ * cookie replies (wgcs_cookie_consume_reply). */
+
+#define WGCS_HS_STATE_ZEROED 0    /* handshakeZeroed */
+#define WGCS_HS_STATE_INITIATED 1 /* handshakeInitiationCreated */
+
+typedef struct wgcs_hs_state { /* 128 B, 4-byte aligned: one handshake in flight */
+  uint32_t state;              /* WGCS_HS_STATE_ZEROED or WGCS_HS_STATE_INITIATED */
+  uint32_t local_index;        /* hs.localIndex: the initiation's sender */
+  uint32_t peer_row;           /* row of the peer table and of d_psk */
+  uint32_t remote_index;       /* msg.Sender of the consumed response, else 0 */
+  uint32_t send_key, recv_key; /* rows of d_keys that receive encrypt / decrypt */
+  uint32_t claim;              /* 0xFFFFFFFF, or the lowest authentic row of the finish launch in flight */
+  uint32_t pad;
+  uint8_t hash[32];            /* after mixHash(msg.Timestamp), noise.go:400 */
+  uint8_t chain_key[32];       /* after the second KDF2, :384-389 */
+  uint8_t ephemeral_private[32];
+} wgcs_hs_state;
+
+typedef struct wgcs_hs_start {   /* 96 B, 4-byte aligned: one initiation to build */
+  uint32_t state_row;            /* row of d_states that receives the handshake */
+  uint32_t peer_row;             /* row of d_table: remote static and precomputedSharedSecret */
+  uint32_t local_index;          /* msg.Sender: the caller's sessions.NewIndex */
+  uint32_t send_key, recv_key;   /* rows of d_keys the finish step will fill */
+  uint32_t flags;                /* bit 0: cookie[] is valid, write MAC2 */
+  uint8_t timestamp[12];         /* the caller's tai64n.Now() */
+  uint8_t pad0[4];
+  uint8_t ephemeral_private[32]; /* the caller's newPrivateKey() */
+  uint8_t cookie[16];
+  uint8_t pad1[8];
+} wgcs_hs_start;
+#define WGCS_HS_START_COOKIE 0x1u
+
+#define WGCS_HS_INITIATED 5 /* the initiation is built and its state row is in place */
+#define WGCS_HS_FINISHED 6  /* the response is authentic: both session keys are in place, the state is zeroed */
+
+/* CreateMessageInitiation (noise.go:344-403) and AddMACs (cookie.go:287-314)
+ * over n descriptors, one lane each: an ordinary launch, asynchronous on
+ * stream (NULL: the context's), n <= 2^28, n == 0 a no-op, aligned 4-byte loads
+ * and stores only, no randomness drawn and no clock read.  d_static_public is
+ * the device's own public key (32 bytes, sealed at :378); d_table holds one
+ * wgcs_peer_key row per peer under the device's private key: public_key is the
+ * remote static and shared is precomputedSharedSecret, so a lane runs two
+ * scalar multiplications (base point x ephemeral, ephemeral x remote static).
+ * n_keys only range-checks the key rows, so that the finish step never has to.
+ * Descriptor j, in this order:
+ *   state_row >= n_states, peer_row >= n_peers, send_key or   d_status[j] = WGCS_ERR_INVALID_ARG; nothing else
+ *   recv_key >= n_keys, or send_key == recv_key                written or read
+ *   the table row's shared is all zero (:381-383), or          WGCS_ERR_LOW_ORDER; the 160 bytes at d_msgs + 160 * j
+ *   X25519(ephemeral, remote static) is (:366-369)             zeroed, the state row untouched
+ *   otherwise                                                  WGCS_HS_INITIATED
+ * For WGCS_HS_INITIATED the 148 bytes at d_msgs + 160 * j are the initiation
+ * with MAC1 under BLAKE2s-256("mac1----" | remote static) and MAC2 (zero
+ * without the cookie flag), and the 12 bytes after them are zero; lastMAC1 is
+ * bytes [116, 132) of that row, should a cookie reply ever need it.  The state
+ * row is written whole: state = WGCS_HS_STATE_INITIATED, local_index,
+ * peer_row, send_key and recv_key from the descriptor, remote_index = 0,
+ * claim = 0xFFFFFFFF, pad = 0, hash, chain_key and ephemeral_private.  Two
+ * descriptors that name one state row are the caller's error, and which of
+ * them wins is unspecified.  Everything is 4-byte aligned.  d_start and
+ * d_states hold the ephemeral private keys for as long as they live. */
+int wgcs_handshake_initiate_batch(wgcs_ctx *ctx, const wgcs_hs_start *d_start, uint32_t n,
+                                  const uint8_t *d_static_public, const wgcs_peer_key *d_table, uint32_t n_peers,
+                                  uint32_t n_keys, wgcs_hs_state *d_states, uint32_t n_states, uint8_t *d_msgs,
+                                  int32_t *d_status, void *stream);
+
+/* ConsumeMessageResponse (noise.go:548-620) and the initiator's
+ * BeginSymmetricSession (:636-662) over the rows of a receive batch, with the
+ * row gating of wgcs_handshake_consume_batch: asynchronous on stream, n <=
+ * 2^28, n == 0 a no-op, the arena only read, d_gate the screen's verdict or
+ * NULL (every row of type 2), d_verdict must not be d_gate.  d_responder is
+ * the device's own wgcs_noise_responder row, of which only private_key is read; d_slots is
+ * a wgcs_session_table_build table that lists local_index -> row of d_states
+ * for the handshakes in flight (n_slots a power of two, or 0); d_psk holds one
+ * 32-byte preshared key per peer row, or is NULL; d_work is scratch of 64
+ * bytes per row.  Row q, in this order, with every state as it stood at launch:
+ *   d_type[q] != 2, or d_gate given and d_gate[q] != WGCS_HS_PASS     d_verdict[q] = WGCS_HS_NONE, nothing else read
+ *   d_pkts[q].len != 92 or LE32 msg[0:4] != 2                         WGCS_ERR_INVALID_ARG           noise.go:549-551
+ *   msg[8:12] not in d_slots, its row >= n_states, that row's
+ *   state != WGCS_HS_STATE_INITIATED or its local_index != msg[8:12]  WGCS_ERR_NO_HANDSHAKE          :553-557, :566
+ *   the state row's peer_row >= n_peers, or a key row >= n_keys       WGCS_ERR_INVALID_ARG
+ *   a shared secret with msg[12:44] is all zero                       WGCS_ERR_LOW_ORDER             :575-584
+ *   msg[44:60] does not open                                          WGCS_ERR_AUTH                  :599-603
+ *   authentic, but a lower row of this launch is authentic for the
+ *   same state row                                                    WGCS_ERR_NO_HANDSHAKE
+ *   otherwise                                                         WGCS_HS_FINISHED
+ * For WGCS_HS_FINISHED d_keys[send_key] = {encrypt, remote_index = msg.Sender,
+ * pad 0} and d_keys[recv_key] = {decrypt, 0, pad 0}, and the state row gets
+ * state = WGCS_HS_STATE_ZEROED, remote_index = msg.Sender, claim = 0xFFFFFFFF
+ * and zeroed hash, chain_key and ephemeral_private (:658-662).  Every other
+ * row writes nothing to d_keys or d_states.  Of several authentic responses to
+ * one handshake the lowest row wins whatever the timing: the call is two
+ * launches, one that only reads the states, leaves verdict and keys in d_work
+ * and takes the minimum of the authentic rows in the state's claim, and one
+ * that commits the rows that hold their claim and zeroes d_work, which is all
+ * zero when the call's work is done.  The reference, taking the rows in turn,
+ * would fail a forged row that follows an authentic one at its state check;
+ * here it fails at its tag (WGCS_ERR_AUTH).  d_pkts is 8-byte aligned,
+ * everything else 4-byte aligned. */
+int wgcs_handshake_finish_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgcs_aead_pkt *d_pkts,
+                                const int32_t *d_type, const int32_t *d_gate, uint32_t n,
+                                const wgcs_noise_responder *d_responder, const wgcs_session_slot *d_slots,
+                                uint32_t n_slots, wgcs_hs_state *d_states, uint32_t n_states, const uint8_t *d_psk,
+                                uint32_t n_peers, wgcs_aead_key *d_keys, uint32_t n_keys, uint8_t *d_work,
+                                int32_t *d_verdict, void *stream);
+
+/* The two batches on host memory, no context and no device: the same row
+ * functions, taken in row order (the finish form in the same two passes), with
+ * the same tables and the same outputs.  They are what a host without a GPU
+ * calls and what the device's outputs are compared with.  WGCS_ERR_INVALID_ARG
+ * for a NULL pointer the device form refuses, n > 2^28 or an n_slots that is
+ * not 0 or a power of two; n == 0 a no-op. */
+int wgcs_handshake_initiate_host(const wgcs_hs_start *start, uint32_t n, const uint8_t *static_public,
+                                 const wgcs_peer_key *table, uint32_t n_peers, uint32_t n_keys, wgcs_hs_state *states,
+                                 uint32_t n_states, uint8_t *msgs, int32_t *status);
+int wgcs_handshake_finish_host(const uint8_t *arena, const wgcs_aead_pkt *pkts, const int32_t *type,
+                               const int32_t *gate, uint32_t n, const wgcs_noise_responder *responder,
+                               const wgcs_session_slot *slots, uint32_t n_slots, wgcs_hs_state *states,
+                               uint32_t n_states, const uint8_t *psk, uint32_t n_peers, wgcs_aead_key *keys,
+                               uint32_t n_keys, uint8_t *work, int32_t *verdict);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,7 @@ ERR_REPLAY = -20
 ERR_MAC1 = -21
 ERR_LOW_ORDER = -22
 ERR_NO_PEER = -23
+ERR_NO_HANDSHAKE = -24
 ERR_HIP = -100
 ERR_NOMEM = -101
 ERR_NO_DEVICE = -102
@@ -52,6 +53,10 @@ HS_NONE, HS_PASS, HS_COOKIE = 0, 1, 2  # wgcs_handshake_screen_batch's verdicts
 HS_CONSUMED = 3  # wgcs_handshake_consume_batch's
 HS_RESPONDED = 4  # wgcs_handshake_respond_batch's
 HS_RESP_COOKIE = 0x1  # wgcs_hs_resp.flags: cookie[] is valid
+HS_INITIATED = 5  # wgcs_handshake_initiate_batch's
+HS_FINISHED = 6  # wgcs_handshake_finish_batch's
+HS_START_COOKIE = 0x1  # wgcs_hs_start.flags: cookie[] is valid
+HS_STATE_ZEROED, HS_STATE_INITIATED = 0, 1  # wgcs_hs_state.state
 PEER_RUNNING = 0x1  # wgcs_peer_key.flags: peer.isRunning
 GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
 
@@ -214,6 +219,10 @@ def load() -> C.CDLL:
         "wgcs_noise_create_response": ([vp, vp, vp, vp, u32, vp, vp, vp, vp], i32),
         "wgcs_noise_consume_response": ([vp, vp, vp, vp, vp, u32, vp, sz, C.POINTER(u32), vp, vp], i32),
         "wgcs_handshake_respond_batch": ([vp, vp, u32, vp, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp], i32),
+        "wgcs_handshake_initiate_batch": ([vp, vp, u32, vp, vp, u32, u32, vp, u32, vp, vp, vp], i32),
+        "wgcs_handshake_finish_batch": ([vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp, vp], i32),
+        "wgcs_handshake_initiate_host": ([vp, u32, vp, vp, u32, u32, vp, u32, vp, vp], i32),
+        "wgcs_handshake_finish_host": ([vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

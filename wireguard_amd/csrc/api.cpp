@@ -254,6 +254,7 @@ const char* wgcs_strerror(int status) {
     case WGCS_ERR_MAC1: return "received packet with invalid mac1";
     case WGCS_ERR_LOW_ORDER: return "bad input point: low order point";
     case WGCS_ERR_NO_PEER: return "no running peer with this public key";
+    case WGCS_ERR_NO_HANDSHAKE: return "no handshake in flight under this receiver index";
     case WGCS_ERR_HIP: return "HIP runtime error";
     case WGCS_ERR_NOMEM: return "out of memory";
     case WGCS_ERR_NO_DEVICE: return "no HIP device";

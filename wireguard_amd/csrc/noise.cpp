@@ -8,9 +8,12 @@
 //   wgcs_noise_create_response       CreateMessageResponse, AddMACs and the responder's keys
 //                                                                   :494-546, :646-651, cookie.go:287-314
 //   wgcs_noise_consume_response      ConsumeMessageResponse and the initiator's keys   :548-620, :638-643
+//   wgcs_handshake_initiate_host     wgcs_handshake_initiate_batch on host memory, row by row
+//   wgcs_handshake_finish_host       wgcs_handshake_finish_batch on host memory, in its two passes
 // They run the scalar code of wgcs_x25519.h and wgcs_noise.h, the code the
-// lanes of noise_kernels.hip run.  Plain C++: the host test programs
-// (tests/noise_host/noise_host.cpp, tests/noise_resp_host/noise_resp_host.cpp)
+// lanes of noise_kernels.hip and noise_init_kernels.hip run.  Plain C++: the
+// host test programs (tests/noise_host/noise_host.cpp,
+// tests/noise_resp_host/noise_resp_host.cpp, tests/noise_init_host/noise_init_host.cpp)
 // link this file as it is.
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>  // the library's build compiles every file as HIP: WGCS_HD's qualifiers
@@ -59,6 +62,8 @@ void start_of(const uint32_t pub[8], uint32_t hash0[8], uint32_t chain0[8]) {
 }
 
 const uint32_t kBasePoint[8] = {9, 0, 0, 0, 0, 0, 0, 0};
+
+constexpr uint32_t kMaxBatch = 1u << 28;  // rows are counted in 32 bits, as in the device forms
 
 }  // namespace
 
@@ -213,6 +218,36 @@ int wgcs_noise_consume_response(const uint8_t static_private[32], const uint8_t 
   if (recv_key) bytes_of(recv, 8, recv_key);
   if (rc == WGCS_OK && sender) *sender = from;
   return rc;
+}
+
+int wgcs_handshake_initiate_host(const wgcs_hs_start* start, uint32_t n, const uint8_t* static_public,
+                                 const wgcs_peer_key* table, uint32_t n_peers, uint32_t n_keys, wgcs_hs_state* states,
+                                 uint32_t n_states, uint8_t* msgs, int32_t* status) {
+  if (n == 0) return WGCS_OK;
+  if (n > kMaxBatch || !start || !static_public || !msgs || !status || (n_peers && !table) || (n_states && !states))
+    return WGCS_ERR_INVALID_ARG;
+  for (uint32_t q = 0; q < n; ++q)
+    status[q] = noise_initiate_row(start + q, static_public, table, n_peers, n_keys, states, n_states,
+                                   msgs + kNoiseInitiationPitch * (size_t)q);
+  return WGCS_OK;
+}
+
+int wgcs_handshake_finish_host(const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* type,
+                               const int32_t* gate, uint32_t n, const wgcs_noise_responder* responder,
+                               const wgcs_session_slot* slots, uint32_t n_slots, wgcs_hs_state* states,
+                               uint32_t n_states, const uint8_t* psk, uint32_t n_peers, wgcs_aead_key* keys,
+                               uint32_t n_keys, uint8_t* work, int32_t* verdict) {
+  if (n == 0) return WGCS_OK;
+  if (n > kMaxBatch || (n_slots & (n_slots - 1)) || !arena || !pkts || !type || !responder || !work || !verdict ||
+      gate == verdict || (n_slots && !slots) || (n_states && !states) || (n_keys && !keys))
+    return WGCS_ERR_INVALID_ARG;
+  // the two launches of the device form, each a loop: every row sees the states as they stood at the call
+  for (uint32_t q = 0; q < n; ++q)
+    verdict[q] = noise_finish_row(q, arena, pkts, type, gate, responder, slots, n_slots, states, n_states, psk, n_peers,
+                                  n_keys, work);
+  for (uint32_t q = 0; q < n; ++q)
+    verdict[q] = noise_finish_commit(q, verdict[q], arena, pkts, slots, n_slots, states, keys, work);
+  return WGCS_OK;
 }
 
 }  // extern "C"

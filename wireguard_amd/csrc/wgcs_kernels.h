@@ -107,4 +107,17 @@ hipError_t launch_hs_respond(const wgcs_hs_resp* resp, uint32_t n, const wgcs_hs
                              uint32_t n_init, const wgcs_peer_key* table, const uint8_t* psk, uint32_t n_peers,
                              wgcs_aead_key* keys, uint32_t n_keys, uint8_t* msgs, int32_t* status, hipStream_t s);
 
+// The initiator's half (noise_init_kernels.hip), one lane per row: n initiations into msgs and
+// the state table, and the responses of a receive batch against that table.  launch_hs_finish
+// is two launches on s, the second of which commits the lowest authentic row per handshake;
+// gate and psk may be NULL.
+hipError_t launch_hs_initiate(const wgcs_hs_start* start, uint32_t n, const uint8_t* static_public,
+                              const wgcs_peer_key* table, uint32_t n_peers, uint32_t n_keys, wgcs_hs_state* states,
+                              uint32_t n_states, uint8_t* msgs, int32_t* status, hipStream_t s);
+hipError_t launch_hs_finish(const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* types, const int32_t* gate,
+                            uint32_t n, const wgcs_noise_responder* self, const wgcs_session_slot* slots,
+                            uint32_t n_slots, wgcs_hs_state* states, uint32_t n_states, const uint8_t* psk,
+                            uint32_t n_peers, wgcs_aead_key* keys, uint32_t n_keys, uint8_t* work, int32_t* verdict,
+                            hipStream_t s);
+
 }  // namespace wgcs

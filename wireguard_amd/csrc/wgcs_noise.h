@@ -1,10 +1,14 @@
 // wgcs_noise.h -- the scalar steps of the reference's Noise_IKpsk2 handshake:
 // the initiation and its consumption (device/noise.go:91-94, :324-457,
 // device/noise_helpers.go:18-58), the response, its consumption and the
-// session keys of both sides (noise.go:494-546, :573-604, :636-655), shared by
-// hs_consume_kernel and hs_respond_kernel (noise_kernels.hip), the host
-// functions of noise.cpp and the host test programs
-// tests/noise_host/noise_host.cpp and tests/noise_resp_host/noise_resp_host.cpp.
+// session keys of both sides (noise.go:494-546, :573-604, :636-655), and the
+// rows of the initiator's two batches over a table of handshake states (the
+// last section), shared by hs_consume_kernel and hs_respond_kernel
+// (noise_kernels.hip), hs_initiate_kernel, hs_finish_kernel and
+// hs_finish_commit_kernel (noise_init_kernels.hip), the host functions of
+// noise.cpp and the host test programs tests/noise_host/noise_host.cpp,
+// tests/noise_resp_host/noise_resp_host.cpp and
+// tests/noise_init_host/noise_init_host.cpp.
 //
 // Everything is little-endian words in registers: a hash, a chaining key, a
 // key, a public key and a shared secret are 8 words, a message is its 37.
@@ -35,6 +39,11 @@
 #include "wgcs_cookie.h"
 #include "wgcs_x25519.h"
 #include "wgcs_xchacha.h"
+
+#pragma push_macro("WGCS_HD")  // wgcs_route_walk.h defines its own, plain inline: keep the forced one of wgcs_poly1305.h
+#undef WGCS_HD
+#include "wgcs_route_walk.h"  // session_get
+#pragma pop_macro("WGCS_HD")
 
 namespace wgcs {
 
@@ -496,6 +505,328 @@ WGCS_HD int noise_consume_response(const uint32_t static_priv[8], const uint32_t
   *sender = m[1];                                  // :614
   noise_kdf2(send_key, recv_key, chain, none, 0);  // :638-643: KDF2(&encryptKey, &decryptKey, chainKey, nil)
   return WGCS_OK;
+}
+
+// ---- the initiator's batches: wgcs_handshake_initiate_batch / _finish_batch and their host
+// forms (include/wgcsum.h).  One row function per step, the same text for a lane of
+// hs_initiate_kernel / hs_finish_kernel / hs_finish_commit_kernel (noise_init_kernels.hip) and
+// for the loops of noise.cpp: struct members are read as they are (4-byte aligned on both
+// sides), byte arrays through noise_load_words / noise_store_words.
+
+constexpr uint32_t kNoiseInitiationPitch = 160;  // a row of d_msgs: the 148 bytes and 12 of zero
+constexpr uint32_t kHsClaimNone = 0xFFFFFFFFu;   // wgcs_hs_state.claim outside a finish call
+constexpr uint32_t kHsWorkWords = 16;            // a row of d_work: encrypt | decrypt
+
+// InitialHash and InitialChainKey of init() (noise.go:91-94): BLAKE2s-256 of the construction
+// name, and of that | the identifier.  noise.cpp computes the same two from the strings.
+WGCS_HD void noise_initial(uint32_t hash[8], uint32_t chain[8]) {
+  const uint32_t h[8] = {0x61B31122u, 0x66C51A08u, 0xDB431269u, 0x32D58A45u,
+                         0x666C9C2Du, 0xB7E89322u, 0x659CE10Eu, 0xF39E07BAu};
+  const uint32_t c[8] = {0xAE6DE260u, 0xC0EF27F3u, 0xE235C32Eu, 0xD0D225A0u,
+                         0x0642EB16u, 0xF57772F8u, 0x98D1382Du, 0x36CD788Bu};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    hash[i] = h[i];
+    chain[i] = c[i];
+  }
+}
+
+// n words of a row's byte array
+WGCS_HD void noise_load_words(const uint8_t* p, uint32_t* w, uint32_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t* const d = (const uint32_t*)p;  // rows are 4-byte aligned on the device
+#pragma unroll
+  for (uint32_t i = 0; i < n; ++i) w[i] = d[i];
+#else
+  for (uint32_t i = 0; i < n; ++i) w[i] = b2s_load_le32(p, 4 * i, 4 * n);
+#endif
+}
+
+// The first N words of the message at p, any alignment.  On the device N + 1 aligned dword
+// loads and a funnel shift by the pointer's low bits (the form of b2s_load_block): the last
+// dword ends at most 4 N + 4 bytes into the message, so N + 1 words of it must exist.
+template <uint32_t N>
+WGCS_HD void noise_msg_words(const uint8_t* p, uint32_t m[N]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t sh = (uint32_t)(uintptr_t)p & 3u;
+  const uint32_t* const w = (const uint32_t*)(p - sh);
+  uint32_t d[N + 1];
+#pragma unroll
+  for (uint32_t i = 0; i < N + 1; ++i) d[i] = w[i];
+#pragma unroll
+  for (uint32_t i = 0; i < N; ++i) m[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], sh);
+#else
+  for (uint32_t i = 0; i < N; ++i) m[i] = b2s_load_le32(p, 4 * i, 4 * N);
+#endif
+}
+
+// noise_create_initiation where the static-static secret is the peer's precomputedSharedSecret
+// (noise.go:305, :381-383), as CreateMessageInitiation itself has it: two scalar
+// multiplications, base point x ephemeral (:361) and ephemeral x remote static (:366), which
+// do not depend on the hashing between them and share one ladder, as the three of
+// noise_create_response do.  The same m, hash and chain as noise_create_initiation gives for
+// precomputed = X25519(static private, remote static); WGCS_ERR_LOW_ORDER, with m zeroed,
+// where that or ephemeral x remote static is all zero.
+WGCS_HD int noise_create_initiation_shared(const uint32_t static_pub[8], const uint32_t remote_static[8],
+                                           const uint32_t precomputed[8], const uint32_t hash0[8],
+                                           const uint32_t chain0[8], const uint32_t eph_priv[8], const uint32_t ts[3],
+                                           uint32_t sender, uint32_t m[37], uint32_t hash[8], uint32_t chain[8]) {
+  uint32_t eph[8], es[8], key[8];
+  bool ok = true;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int i = 0; i < 2; ++i) {  // the step is the same for every lane: no secret decides it
+    uint32_t point[8], r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) point[j] = i == 0 ? (j == 0 ? 9u : 0u) : remote_static[j];
+    ok = x25519_words(eph_priv, point, r) && ok;
+    if (i == 0) {  // :361 hs.localEphemeral.publicKey()
+#pragma unroll
+      for (int j = 0; j < 8; ++j) eph[j] = r[j];
+    } else {  // :366 sharedSecret(hs.remoteStatic)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) es[j] = r[j];
+    }
+  }
+  uint32_t any = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) any |= precomputed[i];
+#pragma unroll
+  for (int i = 0; i < 37; ++i) m[i] = 0;
+  if (!ok || any == 0) return WGCS_ERR_LOW_ORDER;  // :366-369, :381-383
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    hash[i] = hash0[i];
+    chain[i] = chain0[i];
+  }
+  m[0] = kNoiseInitiationType;
+  m[1] = sender;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) m[2 + i] = eph[i];
+  noise_mix_key(chain, eph);  // :363
+  const uint32_t eph12[12] = {eph[0], eph[1], eph[2], eph[3], eph[4], eph[5], eph[6], eph[7], 0, 0, 0, 0};
+  noise_mix_hash(hash, eph12, 32);  // :364
+  // encrypt static key
+  noise_mix_secret(chain, key, es);                       // :371-376
+  noise_seal(key, static_pub, 32, hash, m + 10, m + 18);  // :378
+  noise_mix_hash(hash, m + 10, 48);                       // :379
+  // encrypt timestamp
+  noise_mix_secret(chain, key, precomputed);  // :384-389
+  const uint32_t ts_pt[8] = {ts[0], ts[1], ts[2], 0, 0, 0, 0, 0};
+  uint32_t ts_ct[8], ts_tag[4];
+  noise_seal(key, ts_pt, 12, hash, ts_ct, ts_tag);  // :392
+  m[22] = ts_ct[0];
+  m[23] = ts_ct[1];
+  m[24] = ts_ct[2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) m[25 + i] = ts_tag[i];
+  noise_mix_hash(hash, m + 22, 28);  // :400: m[29..33] are still zero
+  return WGCS_OK;
+}
+
+// The 160 bytes of a d_msgs row at msg from the words of noise_create_initiation_shared, with
+// AddMACs (cookie.go:287-314): MAC1 under mac1_key over the 116 bytes before it, MAC2 under
+// the cookie over the 132 bytes before it, or zero without one, and 12 bytes of zero.  The
+// MACs are taken over the bytes just stored.
+WGCS_HD void noise_write_initiation(uint8_t* msg, const uint32_t m[kNoiseBodyWords], const uint32_t mac1_key[8],
+                                    bool has_cookie, const uint32_t cookie[4]) {
+  uint32_t mac[4];
+  noise_store_words(msg, m, kNoiseBodyWords);
+  cookie_mac128(mac1_key, 32, msg, kNoiseInitiationSize - 2 * kMacSize, mac);  // :296-300
+  noise_store_words(msg + (kNoiseInitiationSize - 2 * kMacSize), mac, 4);
+  if (has_cookie) {
+    const uint32_t key[8] = {cookie[0], cookie[1], cookie[2], cookie[3], 0, 0, 0, 0};
+    cookie_mac128(key, 16, msg, kNoiseInitiationSize - kMacSize, mac);  // :309-313
+  } else {
+    mac[0] = mac[1] = mac[2] = mac[3] = 0;
+  }
+  noise_store_words(msg + (kNoiseInitiationSize - kMacSize), mac, 4);
+  const uint32_t zero[3] = {0, 0, 0};
+  noise_store_words(msg + kNoiseInitiationSize, zero, 3);
+}
+
+// One descriptor of wgcs_handshake_initiate_batch: its status, with the message row at msg
+// and the state row written as that function's table says.
+WGCS_HD int noise_initiate_row(const wgcs_hs_start* d, const uint8_t* static_public, const wgcs_peer_key* table,
+                               uint32_t n_peers, uint32_t n_keys, wgcs_hs_state* states, uint32_t n_states,
+                               uint8_t* msg) {
+  const uint32_t state_row = d->state_row, peer_row = d->peer_row, local_index = d->local_index;
+  const uint32_t send_row = d->send_key, recv_row = d->recv_key, flags = d->flags;
+  if (state_row >= n_states || peer_row >= n_peers || send_row >= n_keys || recv_row >= n_keys || send_row == recv_row)
+    return WGCS_ERR_INVALID_ARG;
+  const wgcs_peer_key* const peer = table + peer_row;
+  uint32_t static_pub[8], remote[8], shared[8], eph_priv[8], ts[3], cookie[4], hash0[8], chain0[8];
+  noise_row_words(static_public, static_pub);
+  noise_row_words(peer->public_key, remote);
+  noise_row_words(peer->shared, shared);
+  noise_row_words(d->ephemeral_private, eph_priv);
+  noise_load_words(d->timestamp, ts, 3);
+  noise_load_words(d->cookie, cookie, 4);
+  noise_initial(hash0, chain0);
+  const uint32_t remote12[12] = {remote[0], remote[1], remote[2], remote[3], remote[4], remote[5],
+                                 remote[6], remote[7], 0,         0,         0,         0};
+  noise_mix_hash(hash0, remote12, 32);  // :358
+  uint32_t m[37], hash[8], chain[8];
+  const int rc =
+      noise_create_initiation_shared(static_pub, remote, shared, hash0, chain0, eph_priv, ts, local_index, m, hash, chain);
+  if (rc != WGCS_OK) {  // a zero shared secret: the state row is not touched
+    noise_store_words(msg, m, 37);
+    const uint32_t zero[3] = {0, 0, 0};
+    noise_store_words(msg + kNoiseInitiationSize, zero, 3);
+    return rc;
+  }
+  uint32_t mac1_key[8];
+  noise_mac1_key(remote, mac1_key);
+  noise_write_initiation(msg, m, mac1_key, (flags & WGCS_HS_START_COOKIE) != 0, cookie);
+  wgcs_hs_state* const st = states + state_row;
+  st->state = WGCS_HS_STATE_INITIATED;
+  st->local_index = local_index;
+  st->peer_row = peer_row;
+  st->remote_index = 0;
+  st->send_key = send_row;
+  st->recv_key = recv_row;
+  st->claim = kHsClaimNone;
+  st->pad = 0;
+  noise_store_words(st->hash, hash, 8);
+  noise_store_words(st->chain_key, chain, 8);
+  noise_store_words(st->ephemeral_private, eph_priv, 8);
+  return WGCS_HS_INITIATED;
+}
+
+// The cryptography of noise_consume_response (noise.go:573-604, :638-643) without its lookup:
+// the two scalar multiplications, ephemeral x msg.Ephemeral (:575) and static x msg.Ephemeral
+// (:581), come first and share one ladder.  WGCS_OK with send_key = encrypt and recv_key =
+// decrypt, or WGCS_ERR_LOW_ORDER / WGCS_ERR_AUTH with both zero.
+WGCS_HD int noise_finish_response(const uint32_t static_priv[8], const uint32_t hash0[8], const uint32_t chain0[8],
+                                  const uint32_t eph_priv[8], const uint32_t psk[8],
+                                  const uint32_t m[kNoiseResponseBodyWords], uint32_t send_key[8],
+                                  uint32_t recv_key[8]) {
+  uint32_t eph[8], ee[8], se[8];
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) eph[i] = m[3 + i];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int i = 0; i < 2; ++i) {  // the step is the same for every lane: no secret decides it
+    uint32_t k[8], r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) k[j] = i == 0 ? eph_priv[j] : static_priv[j];
+    ok = x25519_words(k, eph, r) && ok;
+    if (i == 0) {  // :575 hs.localEphemeral.sharedSecret(msg.Ephemeral)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ee[j] = r[j];
+    } else {  // :581 device.staticIdentity.privateKey.sharedSecret(msg.Ephemeral)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) se[j] = r[j];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) send_key[i] = recv_key[i] = 0;
+  if (!ok) return WGCS_ERR_LOW_ORDER;  // :575-584
+  uint32_t hash[8], chain[8], tau[8], key[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    hash[i] = hash0[i];
+    chain[i] = chain0[i];
+  }
+  const uint32_t eph12[12] = {eph[0], eph[1], eph[2], eph[3], eph[4], eph[5], eph[6], eph[7], 0, 0, 0, 0};
+  noise_mix_hash(hash, eph12, 32);  // :573
+  noise_mix_key(chain, eph);        // :574
+  noise_mix_key(chain, ee);         // :579
+  noise_mix_key(chain, se);         // :585
+  // add preshared key (psk)
+  uint32_t in[16];
+  noise_pad32(psk, in);
+  noise_kdf3(chain, tau, key, chain, in, 32);  // :590-596
+  const uint32_t tau12[12] = {tau[0], tau[1], tau[2], tau[3], tau[4], tau[5], tau[6], tau[7], 0, 0, 0, 0};
+  noise_mix_hash(hash, tau12, 32);  // :597
+  // authenticate transcript
+  const uint32_t none[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t pt[8];
+  if (!noise_open(key, none, 0, m + 11, hash, pt)) return WGCS_ERR_AUTH;  // :599-603
+  noise_kdf2(send_key, recv_key, chain, none, 0);                         // :638-643
+  return WGCS_OK;
+}
+
+// The first pass over row q of wgcs_handshake_finish_batch: its verdict before the duplicate
+// rule.  The states are only read, but for the claim: an authentic row leaves its two keys in
+// its row of work and takes the minimum of q and the state's claim.
+WGCS_HD int noise_finish_row(uint32_t q, const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* types,
+                             const int32_t* gate, const wgcs_noise_responder* self, const wgcs_session_slot* slots,
+                             uint32_t n_slots, wgcs_hs_state* states, uint32_t n_states, const uint8_t* psk_table,
+                             uint32_t n_peers, uint32_t n_keys, uint8_t* work) {
+  if (types[q] != (int32_t)kNoiseResponseType || (gate && gate[q] != WGCS_HS_PASS)) return WGCS_HS_NONE;
+  const wgcs_aead_pkt pk = pkts[q];
+  if (pk.len != kNoiseResponseSize) return WGCS_ERR_INVALID_ARG;
+  uint32_t m[kNoiseResponseBodyWords];
+  noise_msg_words<kNoiseResponseBodyWords>(arena + pk.off, m);
+  if (m[0] != kNoiseResponseType) return WGCS_ERR_INVALID_ARG;  // :549-551
+  const uint32_t row = session_get(slots, n_slots, m[2]);       // :553 sessions.Get(msg.Receiver); empty is past any table
+  if (row >= n_states) return WGCS_ERR_NO_HANDSHAKE;
+  wgcs_hs_state* const st = states + row;
+  if (st->state != WGCS_HS_STATE_INITIATED || st->local_index != m[2]) return WGCS_ERR_NO_HANDSHAKE;  // :566
+  const uint32_t peer_row = st->peer_row;
+  if (peer_row >= n_peers || st->send_key >= n_keys || st->recv_key >= n_keys) return WGCS_ERR_INVALID_ARG;
+  uint32_t priv[8], hash0[8], chain0[8], eph_priv[8], psk[8], keys[kHsWorkWords];
+  noise_row_words(self->private_key, priv);
+  noise_row_words(st->hash, hash0);
+  noise_row_words(st->chain_key, chain0);
+  noise_row_words(st->ephemeral_private, eph_priv);
+  if (psk_table) {
+    noise_row_words(psk_table + 32 * (uint64_t)peer_row, psk);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) psk[i] = 0;
+  }
+  const int rc = noise_finish_response(priv, hash0, chain0, eph_priv, psk, m, keys, keys + 8);
+  if (rc != WGCS_OK) return rc;
+  noise_store_words(work + 4 * kHsWorkWords * (uint64_t)q, keys, kHsWorkWords);
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicMin(&st->claim, q);
+#else
+  if (q < st->claim) st->claim = q;
+#endif
+  return WGCS_HS_FINISHED;
+}
+
+// The second pass: the final verdict of row q from the first pass's.  The authentic row that
+// holds its state's claim writes both key rows and zeroes the handshake (:658-662); the other
+// authentic rows are the copies the reference would meet in a state that is no longer
+// handshakeInitiationCreated.  Every row's work is zeroed.
+WGCS_HD int noise_finish_commit(uint32_t q, int verdict, const uint8_t* arena, const wgcs_aead_pkt* pkts,
+                                const wgcs_session_slot* slots, uint32_t n_slots, wgcs_hs_state* states,
+                                wgcs_aead_key* keys, uint8_t* work) {
+  uint8_t* const mine = work + 4 * kHsWorkWords * (uint64_t)q;
+  const uint32_t zero[kHsWorkWords] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (verdict == WGCS_HS_FINISHED) {
+    uint32_t m[3];
+    noise_msg_words<3>(arena + pkts[q].off, m);
+    wgcs_hs_state* const st = states + session_get(slots, n_slots, m[2]);  // the row the first pass found
+    if (st->claim != q) {  // a lower row's, or kHsClaimNone once that row has committed: never q
+      verdict = WGCS_ERR_NO_HANDSHAKE;
+    } else {
+      uint32_t k[kHsWorkWords];
+      noise_load_words(mine, k, kHsWorkWords);
+      wgcs_aead_key* const ks = keys + st->send_key;
+      wgcs_aead_key* const kr = keys + st->recv_key;
+      noise_store_words(ks->key, k, 8);
+      noise_store_words(kr->key, k + 8, 8);
+      ks->remote_index = m[1];  // the receiver index of every transport message sealed under this key
+      kr->remote_index = 0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) ks->pad[i] = kr->pad[i] = 0;
+      st->state = WGCS_HS_STATE_ZEROED;
+      st->remote_index = m[1];  // :614
+      st->claim = kHsClaimNone;
+      noise_store_words(st->hash, zero, 8);
+      noise_store_words(st->chain_key, zero, 8);
+      noise_store_words(st->ephemeral_private, zero, 8);
+    }
+  }
+  noise_store_words(mine, zero, kHsWorkWords);
+  return verdict;
 }
 
 }  // namespace wgcs

@@ -11,6 +11,10 @@ Names and argument meaning follow the reference:
                                                   BeginSymmetricSession keys, :494-546, :646-651
   consume_response                                ConsumeMessageResponse and the initiator's keys, :548-620, :638-643
   x25519_batch / consume_batch / respond_batch    the same over device-resident rows
+  initiate_batch / finish_batch                   CreateMessageInitiation with AddMACs, and ConsumeMessageResponse
+                                                  with the initiator's keys, over device-resident rows joined by
+                                                  a table of HS_STATE_DTYPE rows, :344-403, :548-620, :636-662
+  initiate_host / finish_host                     those two on host memory (numpy arrays), row by row
 The clock, the randomness and the handshake state are the caller's: the
 ephemeral private keys, the timestamp and the session indices are arguments, and
 what follows noise.go:457 -- the comparison with lastTimestamp, the flood rule,
@@ -27,9 +31,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (ERR_AUTH, ERR_LOW_ORDER, ERR_NO_PEER, HS_CONSUMED, HS_NONE, HS_PASS, HS_RESP_COOKIE, HS_RESPONDED,
-                   PEER_NONE, PEER_RUNNING)
+from ._lib import (ERR_AUTH, ERR_LOW_ORDER, ERR_NO_HANDSHAKE, ERR_NO_PEER, HS_CONSUMED, HS_FINISHED, HS_INITIATED, HS_NONE,
+                   HS_PASS, HS_RESP_COOKIE, HS_RESPONDED, HS_START_COOKIE, HS_STATE_INITIATED, HS_STATE_ZEROED, PEER_NONE,
+                   PEER_RUNNING)
 from .cookie import _fixed, _status
+from .router import SESSION_SLOT_DTYPE
 from .transport import AEAD_KEY_DTYPE, AEAD_PKT_DTYPE, _rows
 from .tun import _ptr
 
@@ -42,15 +48,27 @@ HS_INIT_DTYPE = np.dtype([("peer", "<u4"), ("sender", "<u4"), ("timestamp", "u1"
 HS_RESP_DTYPE = np.dtype([("init_row", "<u4"), ("peer_row", "<u4"), ("local_index", "<u4"), ("send_key", "<u4"),
                           ("recv_key", "<u4"), ("flags", "<u4"), ("pad", "<u4", (2,)), ("ephemeral_private", "u1", (32,)),
                           ("cookie", "u1", (16,))])  # wgcs_hs_resp
+HS_STATE_DTYPE = np.dtype([("state", "<u4"), ("local_index", "<u4"), ("peer_row", "<u4"), ("remote_index", "<u4"),
+                           ("send_key", "<u4"), ("recv_key", "<u4"), ("claim", "<u4"), ("pad", "<u4"),
+                           ("hash", "u1", (32,)), ("chain_key", "u1", (32,)),
+                           ("ephemeral_private", "u1", (32,))])  # wgcs_hs_state
+HS_START_DTYPE = np.dtype([("state_row", "<u4"), ("peer_row", "<u4"), ("local_index", "<u4"), ("send_key", "<u4"),
+                           ("recv_key", "<u4"), ("flags", "<u4"), ("timestamp", "u1", (12,)), ("pad0", "u1", (4,)),
+                           ("ephemeral_private", "u1", (32,)), ("cookie", "u1", (16,)),
+                           ("pad1", "u1", (8,))])  # wgcs_hs_start
 RESPONSE_SIZE, RESPONSE_PITCH = 92, 96  # MessageResponseSize; a row of respond_batch's msgs
+INITIATION_SIZE, INITIATION_PITCH = 148, 160  # MessageInitiationSize; a row of initiate_batch's msgs
+FINISH_WORK_BYTES = 64  # finish_batch's scratch per row
 assert NOISE_RESPONDER_DTYPE.itemsize == 96 and PEER_KEY_DTYPE.itemsize == 72 and HS_INIT_DTYPE.itemsize == 128
-assert HS_RESP_DTYPE.itemsize == 80
+assert HS_RESP_DTYPE.itemsize == 80 and HS_STATE_DTYPE.itemsize == 128 and HS_START_DTYPE.itemsize == 96
 
 __all__ = ["NOISE_RESPONDER_DTYPE", "PEER_KEY_DTYPE", "HS_INIT_DTYPE", "x25519", "responder_init", "peer_keys_build",
            "peer_keys_find", "consume_initiation", "create_initiation", "x25519_batch", "consume_batch", "HS_NONE",
            "HS_PASS", "HS_CONSUMED", "ERR_AUTH", "ERR_LOW_ORDER", "ERR_NO_PEER", "PEER_NONE", "PEER_RUNNING",
            "HS_RESP_DTYPE", "RESPONSE_SIZE", "RESPONSE_PITCH", "create_response", "consume_response", "respond_batch",
-           "HS_RESPONDED", "HS_RESP_COOKIE"]
+           "HS_RESPONDED", "HS_RESP_COOKIE", "HS_STATE_DTYPE", "HS_START_DTYPE", "INITIATION_SIZE", "INITIATION_PITCH",
+           "FINISH_WORK_BYTES", "initiate_batch", "finish_batch", "initiate_host", "finish_host", "HS_INITIATED",
+           "HS_FINISHED", "HS_START_COOKIE", "HS_STATE_ZEROED", "HS_STATE_INITIATED", "ERR_NO_HANDSHAKE"]
 
 
 def _one(x, dtype: np.dtype, what: str) -> np.ndarray:
@@ -207,3 +225,103 @@ def respond_batch(dev, resp, init, gate, table, psk, keys, msgs, status, stream=
     dev._check(dev.lib.wgcs_handshake_respond_batch(dev.h, _ptr(resp), n, _ptr(init) if n_init else None, _ptr(gate),
                                                     n_init, _ptr(table) if n_peers else None, _ptr(psk), n_peers,
                                                     _ptr(keys) if n_keys else None, n_keys, _ptr(msgs), _ptr(status), s))
+
+
+def initiate_batch(dev, start, static_public, table, states, msgs, status, n_keys: int, stream=None, n: int | None = None,
+                   n_peers: int | None = None, n_states: int | None = None) -> None:
+    """Asynchronous wgcs_handshake_initiate_batch over HS_START_DTYPE
+    descriptors: `static_public` is the device's own public key (32 bytes),
+    `table` its PEER_KEY_DTYPE rows (remote static and precomputed secret),
+    `states` the HS_STATE_DTYPE table that finish_batch reads, n_keys the rows of
+    the AEAD key table the descriptors' key rows are checked against.
+    status[j] (int32) = HS_INITIATED, ERR_INVALID_ARG or ERR_LOW_ORDER, and msgs
+    (INITIATION_PITCH bytes per descriptor) and states as the header says.
+    Everything is on the device."""
+    s = getattr(stream, "cuda_stream", stream)
+    n = _rows(start, HS_START_DTYPE) if n is None else n
+    n_peers = (0 if table is None else _rows(table, PEER_KEY_DTYPE)) if n_peers is None else n_peers
+    n_states = (0 if states is None else _rows(states, HS_STATE_DTYPE)) if n_states is None else n_states
+    dev._check(dev.lib.wgcs_handshake_initiate_batch(dev.h, _ptr(start), n, _ptr(static_public),
+                                                     _ptr(table) if n_peers else None, n_peers, n_keys,
+                                                     _ptr(states) if n_states else None, n_states, _ptr(msgs),
+                                                     _ptr(status), s))
+
+
+def finish_batch(dev, arena, pkts, types, gate, responder, slots, states, psk, keys, work, verdict, stream=None,
+                 n: int | None = None, n_slots: int | None = None, n_states: int | None = None,
+                 n_peers: int | None = None, n_keys: int | None = None) -> None:
+    """Asynchronous wgcs_handshake_finish_batch over classify_batch's pkts and
+    types and screen_batch's verdicts as `gate` (None: every row of type 2).
+    `responder` is the device's own NOISE_RESPONDER_DTYPE row, `slots`
+    router.session_table rows that list local_index -> row of `states`, `psk` 32
+    bytes per peer row or None (then give n_peers), `keys` the AEAD_KEY_DTYPE
+    table, `work` FINISH_WORK_BYTES of scratch per row.  verdict[q] (int32) =
+    HS_NONE, HS_FINISHED, ERR_INVALID_ARG, ERR_NO_HANDSHAKE, ERR_LOW_ORDER or
+    ERR_AUTH, and keys and states as the header says.  Everything is on the
+    device."""
+    s = getattr(stream, "cuda_stream", stream)
+    n = _rows(pkts, AEAD_PKT_DTYPE) if n is None else n
+    n_slots = (0 if slots is None else _rows(slots, SESSION_SLOT_DTYPE)) if n_slots is None else n_slots
+    n_states = (0 if states is None else _rows(states, HS_STATE_DTYPE)) if n_states is None else n_states
+    if n_peers is None:
+        if psk is None:
+            raise ValueError("n_peers, where there is no psk table to count")
+        n_peers = _rows(psk, np.dtype(("u1", (32,))))
+    n_keys = (0 if keys is None else _rows(keys, AEAD_KEY_DTYPE)) if n_keys is None else n_keys
+    dev._check(dev.lib.wgcs_handshake_finish_batch(dev.h, _ptr(arena), _ptr(pkts), _ptr(types), _ptr(gate), n,
+                                                   _ptr(responder), _ptr(slots) if n_slots else None, n_slots,
+                                                   _ptr(states) if n_states else None, n_states, _ptr(psk), n_peers,
+                                                   _ptr(keys) if n_keys else None, n_keys, _ptr(work), _ptr(verdict), s))
+
+
+def _host(a, dtype, what: str) -> np.ndarray:
+    """A writable C-contiguous array of `dtype` rows over the caller's memory (no copy: the C side writes it)."""
+    if not isinstance(a, np.ndarray) or not a.flags.c_contiguous or not a.flags.writeable:
+        raise TypeError(f"{what}: a writable C-contiguous numpy array")
+    return a.reshape(-1).view(np.uint8).view(dtype)
+
+
+def initiate_host(start, static_public, table, states, msgs, status, n_keys: int) -> None:
+    """wgcs_handshake_initiate_host: initiate_batch on numpy arrays, row by row.
+    `states` (HS_STATE_DTYPE), `msgs` (uint8, INITIATION_PITCH bytes per
+    descriptor) and `status` (int32) are written in place."""
+    d = np.ascontiguousarray(start, dtype=HS_START_DTYPE).reshape(-1)
+    t = np.ascontiguousarray(table, dtype=PEER_KEY_DTYPE).reshape(-1)
+    st, m, out = _host(states, HS_STATE_DTYPE, "states"), _host(msgs, np.uint8, "msgs"), _host(status, np.int32, "status")
+    if len(m) < INITIATION_PITCH * len(d) or len(out) < len(d):
+        raise ValueError("msgs and status hold one row per descriptor")
+    _status(_lib.load().wgcs_handshake_initiate_host(d.ctypes.data, len(d), _fixed(static_public, 32, "a public key"),
+                                                     t.ctypes.data if len(t) else None, len(t), n_keys,
+                                                     st.ctypes.data if len(st) else None, len(st), m.ctypes.data,
+                                                     out.ctypes.data), "wgcs_handshake_initiate_host")
+
+
+def finish_host(arena, pkts, types, gate, responder, slots, states, psk, keys, work, verdict, n_peers: int | None = None
+                ) -> None:
+    """wgcs_handshake_finish_host: finish_batch on numpy arrays, in its two
+    passes.  `states` (HS_STATE_DTYPE), `keys` (AEAD_KEY_DTYPE), `work` (uint8)
+    and `verdict` (int32) are written in place; gate and psk may be None (then
+    give n_peers)."""
+    a = np.ascontiguousarray(arena, dtype=np.uint8).reshape(-1)
+    p = np.ascontiguousarray(pkts, dtype=AEAD_PKT_DTYPE).reshape(-1)
+    ty = np.ascontiguousarray(types, dtype=np.int32).reshape(-1)
+    g = None if gate is None else np.ascontiguousarray(gate, dtype=np.int32).reshape(-1)
+    r = _one(responder, NOISE_RESPONDER_DTYPE, "NOISE_RESPONDER_DTYPE")
+    sl = np.ascontiguousarray(slots, dtype=SESSION_SLOT_DTYPE).reshape(-1)
+    k = None if psk is None else np.ascontiguousarray(psk, dtype=np.uint8).reshape(-1, 32)
+    st, ks = _host(states, HS_STATE_DTYPE, "states"), _host(keys, AEAD_KEY_DTYPE, "keys")
+    w, out = _host(work, np.uint8, "work"), _host(verdict, np.int32, "verdict")
+    n = len(p)
+    if len(ty) != n or (g is not None and len(g) != n) or len(w) < FINISH_WORK_BYTES * n or len(out) < n:
+        raise ValueError("types, gate, work and verdict hold one row per packet")
+    if n_peers is None:
+        if k is None:
+            raise ValueError("n_peers, where there is no psk table to count")
+        n_peers = len(k)
+    _status(_lib.load().wgcs_handshake_finish_host(a.ctypes.data, p.ctypes.data, ty.ctypes.data,
+                                                   None if g is None else g.ctypes.data, n, r.ctypes.data,
+                                                   sl.ctypes.data if len(sl) else None, len(sl),
+                                                   st.ctypes.data if len(st) else None, len(st),
+                                                   None if k is None else k.ctypes.data, n_peers,
+                                                   ks.ctypes.data if len(ks) else None, len(ks), w.ctypes.data,
+                                                   out.ctypes.data), "wgcs_handshake_finish_host")

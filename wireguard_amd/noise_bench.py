@@ -1,11 +1,27 @@
-"""X25519, handshake-consume and handshake-respond measurement (DESIGN.md
-§4.14, §4.15): the device-resident wgcs_x25519_batch,
-wgcs_handshake_consume_batch and wgcs_handshake_respond_batch on one MI355X,
-beside the same scalar code on one host core.
+"""X25519 and handshake measurement: the
+device-resident wgcs_x25519_batch, wgcs_handshake_consume_batch,
+wgcs_handshake_respond_batch, wgcs_handshake_initiate_batch and
+wgcs_handshake_finish_batch on one MI355X, beside the same scalar code on one
+host core.
 
-  python -m wireguard_amd.noise_bench --mode x25519|consume|respond [--rows 65536 --peers 1024 --steps 20 --warmup 3]
+  python -m wireguard_amd.noise_bench --mode x25519|consume|respond|initiate|finish
+                                      [--rows 65536 --peers 1024 --steps 20 --warmup 3]
 
 Workload:
+  initiate `rows` descriptors, every one of which runs the whole function: state
+           row q and key rows 2q and 2q + 1, the peers in turn, a fresh ephemeral
+           key, timestamp and index each, a cookie on every other one.
+  finish   `rows` responses of 92 B at odd byte offsets of one arena (pitch 97),
+           every row of type 2 with no gate and authentic, each for a state row of
+           its own.  `--distinct` handshakes are made on the host (initiation,
+           the peer's consume and response) and tiled: a tiled row is its state
+           and its response under another index, which the transcript does not
+           cover, so every lane does the whole work and every row ends
+           WGCS_HS_FINISHED.  The call zeroes the states it finishes, so a device
+           copy restores the state table before every launch, inside the timed
+           window (128 B per row, read and written once).
+           Both lines also carry two wgcs_x25519_batch launches of the same
+           `rows` timed in the same process, the floor for two ladders per lane.
   respond  `rows` descriptors over `--distinct` consumed initiations made on the
            host and tiled, no gate, every row runs the whole function: a fresh
            ephemeral key and session index each, a cookie on every other one, a
@@ -29,7 +45,8 @@ anything is timed.
 
 Prints one JSON line: us per launch and rows per second, and in the same line
 the host functions of the C ABI (wgcs_x25519 / wgcs_noise_consume_initiation /
-wgcs_noise_create_response) on one CPU core over the first `--host-rows` rows, called through ctypes, and
+wgcs_noise_create_response, one call per row; wgcs_handshake_initiate_host /
+wgcs_handshake_finish_host, one call for all rows) on one CPU core over the first `--host-rows` rows, called through ctypes, and
 -- as context only -- the X25519 line of `openssl speed -seconds 1 ecdhx25519`
 where that binary exists.
 """
@@ -46,9 +63,10 @@ import numpy as np
 
 from . import _lib, noise
 from .noise import HS_INIT_DTYPE
-from .transport import AEAD_PKT_DTYPE
+from .transport import AEAD_KEY_DTYPE, AEAD_PKT_DTYPE
 
 MSG, PITCH = 148, 150
+RESP_PITCH = 97  # finish: responses at 1 + 97 q, every alignment of the dword loads
 INITIATORS = 16
 
 
@@ -127,9 +145,81 @@ def make_respond(n: int, n_peers: int, distinct: int, seed: int = 20261022):
     return table, init, psk, resp
 
 
+def _peers(rng, n_peers: int):
+    """(private keys of the first INITIATORS peers, every peer's public key)"""
+    privs = [rng.bytes(32) for _ in range(min(INITIATORS, n_peers))]
+    keys = [noise.x25519(k, (9).to_bytes(32, "little")) for k in privs]
+    keys += [noise.x25519(rng.bytes(32), (9).to_bytes(32, "little")) for _ in range(n_peers - len(keys))]
+    return privs, keys
+
+
+def make_initiate(n: int, n_peers: int, seed: int = 20261023, callers: int | None = None):
+    """The initiator's responder row, public key and peer table, and n descriptors:
+    state row q, key rows 2q and 2q + 1, the peers in turn (or only the first
+    `callers` of them, whose private keys are returned), index 1 + q, a cookie on
+    every other one."""
+    rng = np.random.default_rng(seed)
+    me, pub = noise.responder_init(rng.bytes(32))
+    privs, keys = _peers(rng, n_peers)
+    table = noise.peer_keys_build(me, keys, np.arange(n_peers, dtype=np.uint32))
+    row_of_peer = np.zeros(n_peers, np.uint32)
+    row_of_peer[table["peer"]] = np.arange(n_peers, dtype=np.uint32)
+    q = np.arange(n, dtype=np.uint32)
+    start = np.zeros(n, noise.HS_START_DTYPE)
+    start["state_row"], start["send_key"], start["recv_key"] = q, 2 * q, 2 * q + 1
+    start["peer_row"] = row_of_peer[q % (n_peers if callers is None else callers)]
+    start["local_index"], start["flags"] = 1 + q, q & 1
+    start["timestamp"] = rng.integers(0, 256, (n, 12), dtype=np.uint8)
+    start["ephemeral_private"] = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    start["cookie"] = rng.integers(0, 256, (n, 16), dtype=np.uint8)
+    return me, pub, privs, table, start
+
+
+def make_finish(n: int, n_peers: int, distinct: int, seed: int = 20261024):
+    """`distinct` whole handshakes made on the host against the first INITIATORS
+    peers, tiled over n rows: state row q and the response at 1 + 97 q carry the
+    index 1 + q.  A preshared key for every other peer."""
+    from .router import session_table
+
+    rng = np.random.default_rng(seed)
+    m = min(distinct, n)
+    me, pub, privs, table, start = make_initiate(m, n_peers, seed, callers=min(INITIATORS, n_peers))
+    psk = rng.integers(0, 256, (n_peers, 32), dtype=np.uint8)
+    psk[::2] = 0
+    states, msgs, status = np.zeros(m, noise.HS_STATE_DTYPE), np.zeros(m * noise.INITIATION_PITCH, np.uint8), np.zeros(m, np.int32)
+    noise.initiate_host(start, pub, table, states, msgs, status, 2 * m)
+    assert (status == noise.HS_INITIATED).all()
+    sides = []
+    for k in privs:
+        r, _ = noise.responder_init(k)
+        sides.append((r, noise.peer_keys_build(r, [pub], [0])))
+    responses = np.zeros((m, 92), np.uint8)
+    for h in range(m):
+        r, t = sides[h % len(privs)]
+        verdict, init = noise.consume_initiation(r, t, msgs[noise.INITIATION_PITCH * h:noise.INITIATION_PITCH * h + 148].tobytes())
+        assert verdict == noise.HS_CONSUMED
+        key = psk[int(start["peer_row"][h])]
+        rc, msg, _, _ = noise.create_response(init, pub, rng.bytes(32), int(rng.integers(0, 2**32)),
+                                              key.tobytes() if key.any() else None, rng.bytes(16) if h & 1 else None)
+        assert rc == 0
+        responses[h] = np.frombuffer(msg, np.uint8)
+    q = np.arange(n, dtype=np.uint32)
+    all_states = states[q % m].copy()
+    all_states["local_index"], all_states["send_key"], all_states["recv_key"] = 1 + q, 2 * q, 2 * q + 1
+    tiled = responses[q % m].copy()
+    tiled[:, 8:12] = (1 + q).astype("<u4").view(np.uint8).reshape(n, 4)
+    arena = np.zeros(1 + RESP_PITCH * n + 64, np.uint8)
+    at = 1 + RESP_PITCH * q.astype(np.int64)
+    arena[(at[:, None] + np.arange(92)[None, :]).reshape(-1)] = tiled.reshape(-1)
+    pkts = np.zeros(n, AEAD_PKT_DTYPE)
+    pkts["off"], pkts["len"], pkts["key"] = at, 92, 0xFFFFFFFF
+    slots = session_table(1 + q, q)
+    return me, table, psk, all_states, arena, pkts, slots
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--mode", choices=("x25519", "consume", "respond"), required=True)
+    ap.add_argument("--mode", choices=("x25519", "consume", "respond", "initiate", "finish"), required=True)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", type=int, default=65536)
@@ -154,6 +244,7 @@ def main():
     L = _lib.load()
     n = args.rows
     host_n = min(args.host_rows, n)
+    host_path = "the C ABI's host function, one ctypes call per row"
 
     def up(a):
         return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
@@ -221,9 +312,68 @@ def main():
         x_out = torch.zeros(32 * n, dtype=torch.uint8, device="cuda")
         x_status = torch.zeros(n, dtype=torch.int32, device="cuda")
 
-        def floor():
-            for _ in range(3):
-                noise.x25519_batch(dev, x_k, x_u, x_out, x_status, stream=stream, n=n)
+        floor_launches = 3
+    elif args.mode == "initiate":
+        me, pub, _, table, start = make_initiate(n, args.peers)
+        h_states = np.zeros(host_n, noise.HS_STATE_DTYPE)
+        h_msgs, h_status = np.zeros(noise.INITIATION_PITCH * host_n, np.uint8), np.zeros(host_n, np.int32)
+        t0 = time.perf_counter()
+        rc = L.wgcs_handshake_initiate_host(start.ctypes.data, host_n, pub, table.ctypes.data, len(table), 2 * n,
+                                            h_states.ctypes.data, host_n, h_msgs.ctypes.data, h_status.ctypes.data)
+        host_us = (time.perf_counter() - t0) / host_n * 1e6
+        assert rc == 0 and (h_status == noise.HS_INITIATED).all(), "host status"
+        d_start, d_pub, d_table = up(start), up(np.frombuffer(pub, np.uint8)), up(table)
+        d_states = torch.zeros(128 * n, dtype=torch.uint8, device="cuda")
+        d_msgs = torch.zeros(noise.INITIATION_PITCH * n, dtype=torch.uint8, device="cuda")
+        d_status = torch.full((n,), -99, dtype=torch.int32, device="cuda")
+
+        def launch():
+            noise.initiate_batch(dev, d_start, d_pub, d_table, d_states, d_msgs, d_status, 2 * n, stream=stream, n=n,
+                                 n_peers=len(table), n_states=n)
+        launch()
+        torch.cuda.synchronize()
+        assert bool((d_status == noise.HS_INITIATED).all()), "status"
+        assert d_msgs[:noise.INITIATION_PITCH * host_n].cpu().numpy().tobytes() == h_msgs.tobytes(), "device initiations != host"
+        assert d_states[:128 * host_n].cpu().numpy().tobytes() == h_states.tobytes(), "device states != host states"
+        kernel = "hs_initiate_kernel"
+        workload = {"rows": n, "peers": len(table), "cookie_fraction": 0.5}
+        floor_launches, host_path = 2, "wgcs_handshake_initiate_host, one ctypes call for all rows"
+    elif args.mode == "finish":
+        me, table, psk, states, arena, pkts, slots = make_finish(n, args.peers, args.distinct)
+        h_states, h_keys = states[:host_n].copy(), np.zeros(2 * host_n, AEAD_KEY_DTYPE)
+        h_work, h_verdict = np.zeros(noise.FINISH_WORK_BYTES * host_n, np.uint8), np.zeros(host_n, np.int32)
+        h_type = np.full(n, 2, np.int32)
+        t0 = time.perf_counter()
+        rc = L.wgcs_handshake_finish_host(arena.ctypes.data, pkts.ctypes.data, h_type.ctypes.data, None, host_n,
+                                          me.ctypes.data, slots.ctypes.data, len(slots), h_states.ctypes.data, host_n,
+                                          psk.ctypes.data, len(psk), h_keys.ctypes.data, 2 * host_n, h_work.ctypes.data,
+                                          h_verdict.ctypes.data)
+        host_us = (time.perf_counter() - t0) / host_n * 1e6
+        assert rc == 0 and (h_verdict == noise.HS_FINISHED).all(), "host verdicts"
+        d_arena, d_pkts, d_me, d_slots, d_psk = up(arena), up(pkts), up(me), up(slots), up(psk)
+        d_states0 = up(states)
+        d_states = d_states0.clone()
+        d_type = torch.full((n,), 2, dtype=torch.int32, device="cuda")
+        d_keys = torch.zeros(48 * 2 * n, dtype=torch.uint8, device="cuda")
+        d_work = torch.zeros(noise.FINISH_WORK_BYTES * n, dtype=torch.uint8, device="cuda")
+        d_verdict = torch.full((n,), -99, dtype=torch.int32, device="cuda")
+
+        def launch():
+            d_states.copy_(d_states0)  # the call zeroes what it finishes: every launch starts from the same table
+            noise.finish_batch(dev, d_arena, d_pkts, d_type, None, d_me, d_slots, d_states, d_psk, d_keys, d_work,
+                               d_verdict, stream=stream, n=n, n_slots=len(slots), n_states=n, n_peers=len(psk),
+                               n_keys=2 * n)
+        launch()
+        torch.cuda.synchronize()
+        assert bool((d_verdict == noise.HS_FINISHED).all()), "verdicts"
+        assert d_keys[:96 * host_n].cpu().numpy().tobytes() == h_keys.tobytes(), "device keys != host keys"
+        assert d_states[:128 * host_n].cpu().numpy().tobytes() == h_states.tobytes(), "device states != host states"
+        assert not bool(d_work.any()), "d_work"
+        kernel = "hs_finish_kernel + hs_finish_commit_kernel"
+        workload = {"rows": n, "message_bytes": 92, "pitch": RESP_PITCH, "peers": len(table),
+                    "distinct_handshakes": min(args.distinct, n), "psk_fraction": 0.5, "gate": None,
+                    "state_restore": "a device copy of the state table before every launch, inside the timed window"}
+        floor_launches, host_path = 2, "wgcs_handshake_finish_host, one ctypes call for all rows"
     else:
         responder, table, arena, pkts, msgs, is_valid = make_consume(n, args.peers, args.valid, args.distinct)
         rp, tp, row = responder.ctypes.data, table.ctypes.data, np.zeros(1, HS_INIT_DTYPE)
@@ -262,7 +412,15 @@ def main():
     ms = e0.elapsed_time(e1) / args.steps
     rate = n / (ms * 1e-3)
     floor_ms = None
-    if args.mode == "respond":  # the same event pair around K times three X25519 launches, in the same process
+    if args.mode in ("respond", "initiate", "finish"):  # the same event pair around K times the bare X25519 launches
+        if args.mode != "respond":
+            x_k, x_u = (up(a) for a in make_x25519(n))
+            x_out = torch.zeros(32 * n, dtype=torch.uint8, device="cuda")
+            x_status = torch.zeros(n, dtype=torch.int32, device="cuda")
+
+        def floor():
+            for _ in range(floor_launches):
+                noise.x25519_batch(dev, x_k, x_u, x_out, x_status, stream=stream, n=n)
         for _ in range(args.warmup):
             floor()
         e0.record(stream)
@@ -273,16 +431,17 @@ def main():
         floor_ms = e0.elapsed_time(e1) / args.steps
     res = {
         "metric": {"x25519": "x25519_per_s", "consume": "handshake_consume_initiations_per_s",
-                   "respond": "handshake_responses_per_s"}[args.mode],
+                   "respond": "handshake_responses_per_s", "initiate": "handshake_initiations_per_s",
+                   "finish": "handshake_finishes_per_s"}[args.mode],
         "value": round(rate), "unit": "rows/s", "us_per_launch": round(ms * 1e3, 2), "steps": args.steps,
         "warmup": args.warmup, "workload": workload, "kernel": kernel,
         "host_one_core": {"us_per_row": round(host_us, 2), "rows_per_s": round(1e6 / host_us), "rows": host_n,
-                          "path": "the C ABI's host function, one ctypes call per row",
+                          "path": host_path,
                           "device_over_host": round(rate / (1e6 / host_us), 1)},
     }
     if floor_ms is not None:
-        res["three_x25519_launches"] = {"us": round(floor_ms * 1e3, 2), "kernel": "x25519_kernel",
-                                        "respond_over_floor": round(ms / floor_ms, 3)}
+        res[{3: "three", 2: "two"}[floor_launches] + "_x25519_launches"] = {
+            "us": round(floor_ms * 1e3, 2), "kernel": "x25519_kernel", f"{args.mode}_over_floor": round(ms / floor_ms, 3)}
     if not args.no_openssl:
         res["openssl_speed_ecdhx25519"] = openssl_speed()
     print(json.dumps(res), flush=True)
