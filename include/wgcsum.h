@@ -972,9 +972,12 @@ int wgcs_handshake_screen_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgc
  * Everything up to the replay / flood check (:458) is stateless and per
  * message -- no clock, no randomness, no per-peer lock -- and runs here over
  * the batch where it landed.  The comparison with lastTimestamp, the
- * HandshakeInitationRate rule and the handshake-state update (:458-491) stay
- * with the host, for which a row of wgcs_hs_init holds what they need.  For
- * every initiation the host accepts, SendHandshakeResponse (send.go:130-169)
+ * HandshakeInitationRate rule and the handshake-state update (:458-491) need
+ * what a row of wgcs_hs_init holds: the host may run them from rows it reads
+ * back, or wgcs_handshake_accept_batch (the last section) runs them on the
+ * stream against per-peer rows in device memory and writes the descriptors of
+ * the next step.  For
+ * every initiation accepted, SendHandshakeResponse (send.go:130-169)
  * then costs three more scalar multiplications, a KDF3, an empty seal, AddMACs
  * and the key derivation of BeginSymmetricSession: that runs here as well,
  * over one descriptor per accepted initiation, and leaves the 92-byte response
@@ -984,8 +987,8 @@ int wgcs_handshake_screen_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgc
  * host map) are fields of the descriptor.  The initiator's half --
  * CreateMessageInitiation and ConsumeMessageResponse with its session keys --
  * runs here too, joined by a table of handshake states in device memory
- * (wgcs_handshake_initiate_batch and wgcs_handshake_finish_batch, the last
- * section).  What stays with the host is index allocation, lastSentHandshake
+ * (wgcs_handshake_initiate_batch and wgcs_handshake_finish_batch, the section
+ * before the last).  What stays with the host is index allocation, lastSentHandshake
  * and the timers, keypair rotation and the consumption of cookie replies.
  * Nothing here draws randomness or reads a clock. */
 
@@ -1293,6 +1296,113 @@ int wgcs_handshake_finish_host(const uint8_t *arena, const wgcs_aead_pkt *pkts, 
                                const wgcs_session_slot *slots, uint32_t n_slots, wgcs_hs_state *states,
                                uint32_t n_states, const uint8_t *psk, uint32_t n_peers, wgcs_aead_key *keys,
                                uint32_t n_keys, uint8_t *work, int32_t *verdict);
+
+/* ---- the responder's stateful tail: timestamp and flood rules
+ * (device/noise.go:458-491, tai64n/tai64n.go:54, device/constants.go:33) ----
+ * What ConsumeMessageInitiation does after its second AEAD open, between
+ * wgcs_handshake_consume_batch and wgcs_handshake_respond_batch on one stream:
+ * every WGCS_HS_CONSUMED row is judged against a table of wgcs_hs_peer rows in
+ * device memory, the rows that win commit their peer's state, and a dense
+ * array of wgcs_hs_resp descriptors comes out that respond takes as it is.  No
+ * clock is read and no randomness drawn: the caller passes now, and a pool of
+ * tickets (session index, ephemeral private key, two key rows), one per
+ * response it is ready to pay for.  The host keeps lastSentHandshake, the
+ * timers, SetEndpointFromPacket from the verdict rows and the index allocation
+ * behind the tickets.  The initiator's wgcs_hs_state table is not touched. */
+
+#define WGCS_HS_ACCEPTED 7     /* the initiation won its peer's handshake: its descriptor is written */
+#define WGCS_ERR_FLOOD (-25)   /* "handshake flood": within HandshakeInitationRate of the last one  noise.go:469-472 */
+
+#define WGCS_HS_PEER_ZEROED 0   /* handshakeZeroed */
+#define WGCS_HS_PEER_CONSUMED 1 /* handshakeInitiationConsumed */
+#define WGCS_HS_PEER_SEEN 0x1u   /* wgcs_hs_peer.flags bit 0: last_consumption_ns is set (a non-zero time.Time) */
+#define WGCS_HS_PEER_COOKIE 0x2u /* bit 1: cookie[] is valid */
+
+#pragma pack(push, 4)
+typedef struct wgcs_hs_peer {    /* 64 B, 4-byte aligned: row r is the responder's handshake of d_table[r] */
+  uint8_t last_timestamp[12];    /* hs.lastTimestamp, compared as bytes.Compare does */
+  uint32_t state;                /* WGCS_HS_PEER_ZEROED or WGCS_HS_PEER_CONSUMED */
+  int64_t last_consumption_ns;   /* hs.lastInitiationConsumption on the caller's monotonic clock; flags bit 0 */
+  uint32_t flags;                /* WGCS_HS_PEER_SEEN | WGCS_HS_PEER_COOKIE */
+  uint32_t remote_index;         /* hs.remoteIndex: the sender of the last initiation accepted */
+  uint32_t claim;                /* 0xFFFFFFFF, or the lowest candidate row of the accept call in flight */
+  uint8_t cookie[16];            /* peer.cookieGenerator's cookie (cookie.go:287-314): the host writes it and
+                                    flags bit 1 when it consumes a cookie reply; the call only reads them */
+  uint8_t pad[12];               /* zero */
+} wgcs_hs_peer;
+#pragma pack(pop)
+
+typedef struct wgcs_hs_ticket {  /* 48 B, 4-byte aligned: one response the caller is ready to pay for */
+  uint32_t local_index;          /* its sessions.NewIndex */
+  uint32_t send_key, recv_key;   /* rows of the wgcs_aead_key table */
+  uint32_t pad;
+  uint8_t ephemeral_private[32]; /* its newPrivateKey() */
+} wgcs_hs_ticket;
+
+/* rows[id] = the row of table whose peer is id, WGCS_PEER_NONE for an id no row
+ * has: wgcs_hs_init.peer carries the caller's id and not the table row.
+ * INVALID_ARG for a row whose peer is >= n_ids, or a NULL table or rows that
+ * is needed; a duplicated id keeps its lowest row. */
+int wgcs_peer_rows_build(const wgcs_peer_key *table, uint32_t n, uint32_t *rows, uint32_t n_ids);
+
+/* The batch is judged as if its rows were consumed in row order with the clock
+ * standing at now_ns (int64 nanoseconds, the caller's monotonic clock); the
+ * reference reads the clock per message.  Asynchronous on stream (NULL: the
+ * context's), n <= 2^28 and n_tickets <= 2^28, no clock read, no randomness
+ * drawn.  d_gate is consume's d_verdict and may not be d_verdict; d_init is
+ * its d_out, of which a lane reads only peer, sender and timestamp; d_table is
+ * its peer table, d_peer_rows (n_ids words) wgcs_peer_rows_build's rows of it,
+ * d_peers one wgcs_hs_peer per table row.  Row q, in this order:
+ *   d_gate[q] != WGCS_HS_CONSUMED                      d_verdict[q] = d_gate[q]; nothing else read
+ *   d_init[q].peer >= n_ids, d_peer_rows[peer] is
+ *   WGCS_PEER_NONE or >= n_peers, or
+ *   d_table[row].peer != d_init[q].peer                WGCS_ERR_NO_PEER
+ *   otherwise, with last = the peer's last_timestamp and every peer row as it
+ *   stood at the call:
+ *     the peer floods at the start if flags bit 0 is set and
+ *     now_ns - last_consumption_ns <= 20 ms (signed: a clock that went back
+ *     floods too).  If it does not, its winner is its lowest row with
+ *     timestamp > last.
+ *     the winner                                       WGCS_HS_ACCEPTED (WGCS_ERR_BATCH_FULL, below)
+ *     timestamp <= the winner's, or <= last without one   WGCS_ERR_REPLAY      noise.go:458, :461-468
+ *     any other row                                    WGCS_ERR_FLOOD       :459, :469-472
+ * Winners are ranked by row number, ascending, the order in which the
+ * reference would have called NewIndex.  The winner of rank j < n_tickets
+ * commits (:474-488): last_timestamp = timestamp, last_consumption_ns = now_ns,
+ * flags bit 0 set, remote_index = sender, state = WGCS_HS_PEER_CONSUMED; and
+ * writes d_resp[j] = {init_row = q, peer_row = its table row, local_index,
+ * send_key, recv_key and ephemeral_private of d_tickets[j], flags =
+ * WGCS_HS_RESP_COOKIE and the peer row's cookie where its flags bit 1 is set,
+ * else 0 and a zero cookie, pads 0}.  A winner of rank >= n_tickets gets
+ * WGCS_ERR_BATCH_FULL and leaves its peer's state untouched, so that the
+ * initiator's retry is accepted; the other rows of that peer keep the verdicts
+ * they had against it.  No other row changes a peer row; claim is 0xFFFFFFFF
+ * when the call's work is done, as it must be before it.
+ * *d_count = min(winners, n_tickets), the descriptors written.  The tail rows
+ * d_resp[*d_count .. n_tickets) are all zero but for init_row = 0xFFFFFFFF,
+ * which wgcs_handshake_respond_batch answers with WGCS_ERR_INVALID_ARG,
+ * nothing else written or read: launch respond over n_tickets descriptors with
+ * d_gate = NULL, without reading the count.  No ticket secret is copied into a
+ * tail row.  n == 0 sets *d_count = 0, fills all n_tickets descriptors as the
+ * tail and does nothing else.  d_init, d_table, d_peer_rows and d_tickets are
+ * only read.  Which wave runs first does not change the outcome: the call is
+ * four launches (claim by atomicMin, verdicts and winners per block, a scan of
+ * the block counts, commit), over a per-block word of scratch the context
+ * owns; a call on another stream of the same context waits for the one before
+ * it.  INVALID_ARG for a NULL pointer that is needed (d_count always),
+ * d_verdict == d_gate, a count over 2^28 or a pointer that is not 4-byte
+ * aligned. */
+int wgcs_handshake_accept_batch(wgcs_ctx *ctx, const wgcs_hs_init *d_init, const int32_t *d_gate, uint32_t n,
+                                int64_t now_ns, const wgcs_peer_key *d_table, const uint32_t *d_peer_rows,
+                                uint32_t n_ids, wgcs_hs_peer *d_peers, uint32_t n_peers,
+                                const wgcs_hs_ticket *d_tickets, uint32_t n_tickets, wgcs_hs_resp *d_resp,
+                                uint32_t *d_count, int32_t *d_verdict, void *stream);
+/* The same contract over host memory, no context and no device: the same row
+ * functions in the same passes. */
+int wgcs_handshake_accept_host(const wgcs_hs_init *init, const int32_t *gate, uint32_t n, int64_t now_ns,
+                               const wgcs_peer_key *table, const uint32_t *peer_rows, uint32_t n_ids,
+                               wgcs_hs_peer *peers, uint32_t n_peers, const wgcs_hs_ticket *tickets,
+                               uint32_t n_tickets, wgcs_hs_resp *resp, uint32_t *count, int32_t *verdict);
 
 #ifdef __cplusplus
 }

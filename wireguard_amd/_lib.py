@@ -40,6 +40,7 @@ ERR_MAC1 = -21
 ERR_LOW_ORDER = -22
 ERR_NO_PEER = -23
 ERR_NO_HANDSHAKE = -24
+ERR_FLOOD = -25
 ERR_HIP = -100
 ERR_NOMEM = -101
 ERR_NO_DEVICE = -102
@@ -57,6 +58,9 @@ HS_INITIATED = 5  # wgcs_handshake_initiate_batch's
 HS_FINISHED = 6  # wgcs_handshake_finish_batch's
 HS_START_COOKIE = 0x1  # wgcs_hs_start.flags: cookie[] is valid
 HS_STATE_ZEROED, HS_STATE_INITIATED = 0, 1  # wgcs_hs_state.state
+HS_ACCEPTED = 7  # wgcs_handshake_accept_batch's
+HS_PEER_ZEROED, HS_PEER_CONSUMED = 0, 1  # wgcs_hs_peer.state
+HS_PEER_SEEN, HS_PEER_COOKIE = 0x1, 0x2  # wgcs_hs_peer.flags: the peer has consumed before; cookie[] is valid
 PEER_RUNNING = 0x1  # wgcs_peer_key.flags: peer.isRunning
 GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
 
@@ -223,6 +227,9 @@ def load() -> C.CDLL:
         "wgcs_handshake_finish_batch": ([vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp, vp], i32),
         "wgcs_handshake_initiate_host": ([vp, u32, vp, vp, u32, u32, vp, u32, vp, vp], i32),
         "wgcs_handshake_finish_host": ([vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp], i32),
+        "wgcs_peer_rows_build": ([vp, u32, vp, u32], i32),
+        "wgcs_handshake_accept_batch": ([vp, vp, vp, u32, C.c_int64, vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp], i32),
+        "wgcs_handshake_accept_host": ([vp, vp, u32, C.c_int64, vp, vp, u32, vp, u32, vp, u32, vp, vp, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

@@ -130,10 +130,12 @@ int wgcs_init(int device, wgcs_ctx** out) {
   for (int j = 1; j < WGCS_MAX_BATCH_STREAMS && e == hipSuccess; ++j)
     e = hipEventCreateWithFlags(&ctx->join_ev[j], hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->accept_ev, hipEventDisableTiming);
   if (e != hipSuccess) {
     for (hipEvent_t ev : ctx->join_ev)
       if (ev) hipEventDestroy(ev);
     if (ctx->fork_ev) hipEventDestroy(ctx->fork_ev);
+    if (ctx->accept_ev) hipEventDestroy(ctx->accept_ev);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
     return WGCS_ERR_HIP;
@@ -216,7 +218,7 @@ int wgcs_destroy(wgcs_ctx* ctx) {
   hipSetDevice(ctx->device);
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
   for (const auto& r : ctx->host_allocs) hipHostFree((void*)r.first);
-  for (DevBuf* b : {&ctx->d_arena, &ctx->d_pkts, &ctx->d_init, &ctx->d_out, &ctx->d_out2, &ctx->d_aux})
+  for (DevBuf* b : {&ctx->d_arena, &ctx->d_pkts, &ctx->d_init, &ctx->d_out, &ctx->d_out2, &ctx->d_aux, &ctx->d_accept})
     if (b->ptr) hipFree(b->ptr);
   for (HostBuf* b : {&ctx->h_stage, &ctx->h_meta, &ctx->h_out})
     if (b->ptr) hipHostFree(b->ptr);
@@ -224,6 +226,7 @@ int wgcs_destroy(wgcs_ctx* ctx) {
   for (hipEvent_t ev : ctx->join_ev)
     if (ev) hipEventDestroy(ev);
   if (ctx->fork_ev) hipEventDestroy(ctx->fork_ev);
+  if (ctx->accept_ev) hipEventDestroy(ctx->accept_ev);
   delete ctx;
   return WGCS_OK;
 }
@@ -255,6 +258,7 @@ const char* wgcs_strerror(int status) {
     case WGCS_ERR_LOW_ORDER: return "bad input point: low order point";
     case WGCS_ERR_NO_PEER: return "no running peer with this public key";
     case WGCS_ERR_NO_HANDSHAKE: return "no handshake in flight under this receiver index";
+    case WGCS_ERR_FLOOD: return "handshake flood";
     case WGCS_ERR_HIP: return "HIP runtime error";
     case WGCS_ERR_NOMEM: return "out of memory";
     case WGCS_ERR_NO_DEVICE: return "no HIP device";

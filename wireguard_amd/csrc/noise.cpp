@@ -10,11 +10,13 @@
 //   wgcs_noise_consume_response      ConsumeMessageResponse and the initiator's keys   :548-620, :638-643
 //   wgcs_handshake_initiate_host     wgcs_handshake_initiate_batch on host memory, row by row
 //   wgcs_handshake_finish_host       wgcs_handshake_finish_batch on host memory, in its two passes
+//   wgcs_peer_rows_build             peer id -> row of the peer table
+//   wgcs_handshake_accept_host       wgcs_handshake_accept_batch on host memory, in its passes   :458-491
 // They run the scalar code of wgcs_x25519.h and wgcs_noise.h, the code the
-// lanes of noise_kernels.hip and noise_init_kernels.hip run.  Plain C++: the
-// host test programs (tests/noise_host/noise_host.cpp,
-// tests/noise_resp_host/noise_resp_host.cpp, tests/noise_init_host/noise_init_host.cpp)
-// link this file as it is.
+// lanes of noise_kernels.hip, noise_init_kernels.hip and noise_accept_kernels.hip
+// run.  Plain C++: the host test programs (tests/noise_host/noise_host.cpp,
+// tests/noise_resp_host/noise_resp_host.cpp, tests/noise_init_host/noise_init_host.cpp,
+// tests/noise_accept_host/noise_accept_host.cpp) link this file as it is.
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>  // the library's build compiles every file as HIP: WGCS_HD's qualifiers
 #endif
@@ -247,6 +249,36 @@ int wgcs_handshake_finish_host(const uint8_t* arena, const wgcs_aead_pkt* pkts, 
                                   n_keys, work);
   for (uint32_t q = 0; q < n; ++q)
     verdict[q] = noise_finish_commit(q, verdict[q], arena, pkts, slots, n_slots, states, keys, work);
+  return WGCS_OK;
+}
+
+int wgcs_peer_rows_build(const wgcs_peer_key* table, uint32_t n, uint32_t* rows, uint32_t n_ids) {
+  if ((n && !table) || (n_ids && !rows)) return WGCS_ERR_INVALID_ARG;
+  for (uint32_t i = 0; i < n; ++i)
+    if (table[i].peer >= n_ids) return WGCS_ERR_INVALID_ARG;
+  for (uint32_t id = 0; id < n_ids; ++id) rows[id] = WGCS_PEER_NONE;
+  for (uint32_t i = n; i-- > 0;) rows[table[i].peer] = i;  // a duplicated id keeps its lowest row
+  return WGCS_OK;
+}
+
+int wgcs_handshake_accept_host(const wgcs_hs_init* init, const int32_t* gate, uint32_t n, int64_t now_ns,
+                               const wgcs_peer_key* table, const uint32_t* peer_rows, uint32_t n_ids,
+                               wgcs_hs_peer* peers, uint32_t n_peers, const wgcs_hs_ticket* tickets,
+                               uint32_t n_tickets, wgcs_hs_resp* resp, uint32_t* count, int32_t* verdict) {
+  if (!count || (n && (!init || !gate || !verdict)) || (n_tickets && (!tickets || !resp)) ||
+      (n && n_peers && (!table || !peers)) || (n && n_ids && !peer_rows) || (n && (const int32_t*)verdict == gate) ||
+      n > kMaxBatch || n_tickets > kMaxBatch)
+    return WGCS_ERR_INVALID_ARG;
+  // the passes of the device form, each a loop: every row sees the peer rows as they stood at the call
+  for (uint32_t q = 0; q < n; ++q)
+    verdict[q] = noise_accept_claim(q, init, gate, now_ns, table, peer_rows, n_ids, peers, n_peers);
+  for (uint32_t q = 0; q < n; ++q) verdict[q] = noise_accept_verdict(q, verdict[q], init, n, peer_rows, peers);
+  uint32_t winners = 0;  // the device form's scan: the winners in the rows below q
+  for (uint32_t q = 0; q < n; ++q)
+    if (verdict[q] == WGCS_HS_ACCEPTED && gate[q] == WGCS_HS_CONSUMED)  // not a verdict passed through
+      verdict[q] = noise_accept_commit(q, winners++, now_ns, init, peer_rows, peers, tickets, n_tickets, resp);
+  *count = winners < n_tickets ? winners : n_tickets;
+  for (uint32_t j = *count; j < n_tickets; ++j) noise_accept_tail(resp + j);
   return WGCS_OK;
 }
 

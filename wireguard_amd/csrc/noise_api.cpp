@@ -4,7 +4,8 @@
 //   wgcs_handshake_respond_batch    CreateMessageResponse, AddMACs, the responder's keys   :494-546, :646-651
 //   wgcs_handshake_initiate_batch   CreateMessageInitiation, AddMACs, the handshake state  :344-403
 //   wgcs_handshake_finish_batch     ConsumeMessageResponse, the initiator's keys           :548-620, :636-662
-// They run in noise_kernels.hip and noise_init_kernels.hip; the responder, the
+//   wgcs_handshake_accept_batch     the timestamp and flood rules, the responder's state     :458-491
+// They run in noise_kernels.hip, noise_init_kernels.hip and noise_accept_kernels.hip; the responder, the
 // tables and the rows are the caller's device memory.  The host functions of
 // the same sections are in noise.cpp.
 #include <hip/hip_runtime.h>
@@ -125,6 +126,41 @@ int wgcs_handshake_finish_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const wgc
       launch_hs_finish(d_arena, d_pkts, d_type, d_gate, n, d_responder, d_slots, n_slots, d_states, n_states, d_psk,
                        n_peers, d_keys, n_keys, d_work, d_verdict, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "handshake_finish launch");
+}
+
+int wgcs_handshake_accept_batch(wgcs_ctx* ctx, const wgcs_hs_init* d_init, const int32_t* d_gate, uint32_t n,
+                                int64_t now_ns, const wgcs_peer_key* d_table, const uint32_t* d_peer_rows,
+                                uint32_t n_ids, wgcs_hs_peer* d_peers, uint32_t n_peers,
+                                const wgcs_hs_ticket* d_tickets, uint32_t n_tickets, wgcs_hs_resp* d_resp,
+                                uint32_t* d_count, int32_t* d_verdict, void* stream) {
+  if (!ctx) return WGCS_ERR_INVALID_ARG;
+  if (!d_count || (n && (!d_init || !d_gate || !d_verdict)) || (n_tickets && (!d_tickets || !d_resp)) ||
+      (n && n_peers && (!d_table || !d_peers)) || (n && n_ids && !d_peer_rows))
+    return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
+  if (n && (const int32_t*)d_verdict == d_gate) return set_err(ctx, WGCS_ERR_INVALID_ARG, "d_verdict must not be d_gate");
+  if (n > kMaxBatch || n_tickets > kMaxBatch || ((uintptr_t)d_init & 3) || ((uintptr_t)d_gate & 3) ||
+      ((uintptr_t)d_table & 3) || ((uintptr_t)d_peer_rows & 3) || ((uintptr_t)d_peers & 3) ||
+      ((uintptr_t)d_tickets & 3) || ((uintptr_t)d_resp & 3) || ((uintptr_t)d_count & 3) || ((uintptr_t)d_verdict & 3))
+    return set_err(ctx, WGCS_ERR_INVALID_ARG,
+                   "n and n_tickets <= 2^28, 4-byte aligned d_init / d_gate / d_table / d_peer_rows / d_peers / "
+                   "d_tickets / d_resp / d_count / d_verdict");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  hipSetDevice(ctx->device);
+  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipError_t e;
+  // the block counts are the context's: the call before this one, if another stream holds it, is done with them first
+  if (ctx->accept_pending && ctx->accept_stream != s &&
+      (e = hipStreamWaitEvent(s, ctx->accept_ev, 0)) != hipSuccess)
+    return hip_fail(ctx, e, "handshake_accept stream order");
+  const int rc = ensure_dev(ctx, ctx->d_accept, sizeof(uint32_t) * (size_t)(hs_accept_blocks(n) + 1));
+  if (rc != WGCS_OK) return rc;
+  e = launch_hs_accept(d_init, d_gate, n, now_ns, d_table, d_peer_rows, n_ids, d_peers, n_peers, d_tickets, n_tickets,
+                       d_resp, d_count, d_verdict, (uint32_t*)ctx->d_accept.ptr, s);
+  if (e != hipSuccess) return hip_fail(ctx, e, "handshake_accept launch");
+  if ((e = hipEventRecord(ctx->accept_ev, s)) != hipSuccess) return hip_fail(ctx, e, "handshake_accept event");
+  ctx->accept_stream = s;
+  ctx->accept_pending = true;
+  return WGCS_OK;
 }
 
 }  // extern "C"

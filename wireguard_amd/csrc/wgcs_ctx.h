@@ -69,6 +69,12 @@ struct wgcs_ctx {
   hipEvent_t join_ev[WGCS_MAX_BATCH_STREAMS] = {};
   // recorded on streams[0] behind the last launch of a fused call; the other listed streams wait on it
   hipEvent_t fork_ev = nullptr;
+  // wgcs_handshake_accept_batch: one word per 256 rows between its launches, the event recorded behind its last
+  // launch (made by wgcs_init) and the stream that holds it; a call on another stream waits on the event first
+  wgcs::DevBuf d_accept;
+  hipEvent_t accept_ev = nullptr;
+  hipStream_t accept_stream = nullptr;
+  bool accept_pending = false;
   bool fuse = true;  // WGCS_FUSE: wgcs_checksum_batches launches groups of batches (wgcs_batch_plan.h)
   // wgcs_host_alloc allocations (device-readable pinned memory): [start, end),
   // the live write stagers, whose zero-copy pushes point into them, and the

@@ -120,4 +120,14 @@ hipError_t launch_hs_finish(const uint8_t* arena, const wgcs_aead_pkt* pkts, con
                             uint32_t n_peers, wgcs_aead_key* keys, uint32_t n_keys, uint8_t* work, int32_t* verdict,
                             hipStream_t s);
 
+// The responder's stateful tail (noise_accept_kernels.hip), one lane per row: four launches on
+// s -- claim, verdict with the winners of each 256-row block counted, a one-block scan of
+// those counts, commit with the tail descriptors -- or two (scan, commit) when n == 0.
+// block_winners is scratch of hs_accept_blocks(n) words, which the call owns until it is done.
+inline uint32_t hs_accept_blocks(uint32_t n) { return n / 256 + (n % 256 != 0); }
+hipError_t launch_hs_accept(const wgcs_hs_init* init, const int32_t* gate, uint32_t n, int64_t now,
+                            const wgcs_peer_key* table, const uint32_t* peer_rows, uint32_t n_ids, wgcs_hs_peer* peers,
+                            uint32_t n_peers, const wgcs_hs_ticket* tickets, uint32_t n_tickets, wgcs_hs_resp* resp,
+                            uint32_t* count, int32_t* verdict, uint32_t* block_winners, hipStream_t s);
+
 }  // namespace wgcs

@@ -3,12 +3,14 @@
 // device/noise_helpers.go:18-58), the response, its consumption and the
 // session keys of both sides (noise.go:494-546, :573-604, :636-655), and the
 // rows of the initiator's two batches over a table of handshake states (the
-// last section), shared by hs_consume_kernel and hs_respond_kernel
+// section before the last), shared by hs_consume_kernel and hs_respond_kernel
 // (noise_kernels.hip), hs_initiate_kernel, hs_finish_kernel and
-// hs_finish_commit_kernel (noise_init_kernels.hip), the host functions of
-// noise.cpp and the host test programs tests/noise_host/noise_host.cpp,
-// tests/noise_resp_host/noise_resp_host.cpp and
-// tests/noise_init_host/noise_init_host.cpp.
+// hs_finish_commit_kernel (noise_init_kernels.hip), the kernels of
+// noise_accept_kernels.hip (the timestamp and flood rules, noise.go:458-491, the
+// last section), the host functions of noise.cpp and the host test programs
+// tests/noise_host/noise_host.cpp, tests/noise_resp_host/noise_resp_host.cpp,
+// tests/noise_init_host/noise_init_host.cpp and
+// tests/noise_accept_host/noise_accept_host.cpp.
 //
 // Everything is little-endian words in registers: a hash, a chaining key, a
 // key, a public key and a shared secret are 8 words, a message is its 37.
@@ -827,6 +829,138 @@ WGCS_HD int noise_finish_commit(uint32_t q, int verdict, const uint8_t* arena, c
   }
   noise_store_words(mine, zero, kHsWorkWords);
   return verdict;
+}
+
+// ---- the responder's stateful tail: wgcs_handshake_accept_batch and its host form
+// (include/wgcsum.h), noise.go:458-491 for a batch judged in row order under one clock value.
+// Three row functions, the same text for a lane of hs_accept_claim_kernel /
+// hs_accept_verdict_kernel / hs_accept_commit_kernel (noise_accept_kernels.hip) and for the
+// loops of noise.cpp.  Of a wgcs_hs_init row only peer, sender and timestamp are read.
+
+constexpr int64_t kHandshakeInitiationRateNs = 20000000;  // HandshakeInitationRate = time.Second / 50, constants.go:33
+constexpr uint32_t kHsRespNone = 0xFFFFFFFFu;             // init_row of a descriptor that holds no response
+
+// a.After(b), tai64n.go:54: bytes.Compare over the 12 bytes, which the words hold little-endian
+WGCS_HD bool noise_timestamp_after(const uint32_t a[3], const uint32_t b[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const uint32_t x = noise_bswap(a[i]), y = noise_bswap(b[i]);
+    if (x != y) return x > y;
+  }
+  return false;
+}
+
+// the row of table and of peers that the initiation's peer id names, or WGCS_PEER_NONE
+WGCS_HD uint32_t noise_accept_peer_row(const wgcs_hs_init* in, const wgcs_peer_key* table, const uint32_t* peer_rows,
+                                       uint32_t n_ids, uint32_t n_peers) {
+  const uint32_t peer = in->peer;
+  if (peer >= n_ids) return WGCS_PEER_NONE;
+  const uint32_t row = peer_rows[peer];
+  if (row == WGCS_PEER_NONE || row >= n_peers || table[row].peer != peer) return WGCS_PEER_NONE;
+  return row;
+}
+
+// time.Since(hs.lastInitiationConsumption) <= HandshakeInitationRate (:459) with the clock at
+// now; a peer that never consumed holds Go's zero time and does not flood.  No signed overflow:
+// the difference is taken only where it is positive.
+WGCS_HD bool noise_accept_flooding(const wgcs_hs_peer* p, int64_t now) {
+  if (!(p->flags & WGCS_HS_PEER_SEEN)) return false;
+  const int64_t last = p->last_consumption_ns;
+  return now <= last || (uint64_t)now - (uint64_t)last <= (uint64_t)kHandshakeInitiationRateNs;
+}
+
+// The first pass over row q: consume's verdict passed through, WGCS_ERR_NO_PEER, or
+// WGCS_HS_CONSUMED for a row the second pass judges.  The peer rows are only read, but for the
+// claim: a row that the peer's state at the call would accept (:458-459) takes the minimum of q
+// and the claim.
+WGCS_HD int noise_accept_claim(uint32_t q, const wgcs_hs_init* init, const int32_t* gate, int64_t now,
+                               const wgcs_peer_key* table, const uint32_t* peer_rows, uint32_t n_ids,
+                               wgcs_hs_peer* peers, uint32_t n_peers) {
+  const int g = gate[q];
+  if (g != WGCS_HS_CONSUMED) return g;
+  const wgcs_hs_init* const in = init + q;
+  const uint32_t row = noise_accept_peer_row(in, table, peer_rows, n_ids, n_peers);
+  if (row == WGCS_PEER_NONE) return WGCS_ERR_NO_PEER;
+  wgcs_hs_peer* const p = peers + row;
+  if (!noise_accept_flooding(p, now)) {
+    uint32_t ts[3], last[3];
+    noise_load_words(in->timestamp, ts, 3);
+    noise_load_words(p->last_timestamp, last, 3);
+    if (noise_timestamp_after(ts, last)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      // A flood is thousands of rows of one peer: a plain look first keeps all but the low rows off the
+      // atomic unit.  The claim only falls, so a stale value costs an atomic and never a claim.
+      if (q < __hip_atomic_load(&p->claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&p->claim, q);
+#else
+      if (q < p->claim) p->claim = q;
+#endif
+    }
+  }
+  return WGCS_HS_CONSUMED;
+}
+
+// The second pass: the verdict of a row the first pass left at WGCS_HS_CONSUMED, with every
+// claim final and no peer row written yet.  The row that holds its peer's claim is the one the
+// reference, taking the rows in turn, accepts; behind it lastTimestamp is its timestamp and
+// lastInitiationConsumption is now, so a later row is a replay (:458, tested first, :461) or
+// floods (:459, :469); a row in front of it was a replay of the stored timestamp, which is below
+// the winner's.  Without a winner the stored timestamp decides.
+WGCS_HD int noise_accept_verdict(uint32_t q, int verdict, const wgcs_hs_init* init, uint32_t n,
+                                 const uint32_t* peer_rows, const wgcs_hs_peer* peers) {
+  if (verdict != WGCS_HS_CONSUMED) return verdict;
+  const wgcs_hs_init* const in = init + q;
+  const wgcs_hs_peer* const p = peers + peer_rows[in->peer];  // the row the first pass found
+  const uint32_t claim = p->claim;
+  if (claim == q) return WGCS_HS_ACCEPTED;
+  uint32_t ts[3], bar[3];
+  noise_load_words(in->timestamp, ts, 3);
+  // a claim is a row of this call or kHsClaimNone; one the caller left behind is taken for none
+  noise_load_words(claim < n ? init[claim].timestamp : p->last_timestamp, bar, 3);
+  return noise_timestamp_after(ts, bar) ? WGCS_ERR_FLOOD : WGCS_ERR_REPLAY;
+}
+
+// The third pass, for a WGCS_HS_ACCEPTED row only: rank counts the winners in the rows below q.
+// With a ticket the winner commits its peer's state (:474-488) and writes its descriptor;
+// without one it only gives the claim back.
+WGCS_HD int noise_accept_commit(uint32_t q, uint32_t rank, int64_t now, const wgcs_hs_init* init,
+                                const uint32_t* peer_rows, wgcs_hs_peer* peers, const wgcs_hs_ticket* tickets,
+                                uint32_t n_tickets, wgcs_hs_resp* resp) {
+  const wgcs_hs_init* const in = init + q;
+  const uint32_t row = peer_rows[in->peer];
+  wgcs_hs_peer* const p = peers + row;
+  p->claim = kHsClaimNone;
+  if (rank >= n_tickets) return WGCS_ERR_BATCH_FULL;
+  uint32_t ts[3], eph[8], cookie[4] = {0, 0, 0, 0};
+  noise_load_words(in->timestamp, ts, 3);
+  const uint32_t flags = p->flags;
+  noise_store_words(p->last_timestamp, ts, 3);  // :480-482
+  p->last_consumption_ns = now;                 // :483-486: now is after it, or the peer would have flooded
+  p->flags = flags | WGCS_HS_PEER_SEEN;
+  p->remote_index = in->sender;                 // :477
+  p->state = WGCS_HS_PEER_CONSUMED;             // :487
+  const wgcs_hs_ticket* const t = tickets + rank;
+  wgcs_hs_resp* const r = resp + rank;
+  r->init_row = q;
+  r->peer_row = row;
+  r->local_index = t->local_index;
+  r->send_key = t->send_key;
+  r->recv_key = t->recv_key;
+  r->flags = (flags & WGCS_HS_PEER_COOKIE) ? WGCS_HS_RESP_COOKIE : 0;
+  r->pad[0] = r->pad[1] = 0;
+  noise_load_words(t->ephemeral_private, eph, 8);
+  noise_store_words(r->ephemeral_private, eph, 8);
+  if (flags & WGCS_HS_PEER_COOKIE) noise_load_words(p->cookie, cookie, 4);
+  noise_store_words(r->cookie, cookie, 4);
+  return WGCS_HS_ACCEPTED;
+}
+
+// a descriptor past the count: no response, which wgcs_handshake_respond_batch turns away unread
+WGCS_HD void noise_accept_tail(wgcs_hs_resp* r) {
+  const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  r->init_row = kHsRespNone;
+  r->peer_row = r->local_index = r->send_key = r->recv_key = r->flags = r->pad[0] = r->pad[1] = 0;
+  noise_store_words(r->ephemeral_private, zero, 8);
+  noise_store_words(r->cookie, zero, 4);
 }
 
 }  // namespace wgcs

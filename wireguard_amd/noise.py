@@ -15,11 +15,14 @@ Names and argument meaning follow the reference:
                                                   with the initiator's keys, over device-resident rows joined by
                                                   a table of HS_STATE_DTYPE rows, :344-403, :548-620, :636-662
   initiate_host / finish_host                     those two on host memory (numpy arrays), row by row
-The clock, the randomness and the handshake state are the caller's: the
-ephemeral private keys, the timestamp and the session indices are arguments, and
-what follows noise.go:457 -- the comparison with lastTimestamp, the flood rule,
-the state update -- takes a HS_INIT_DTYPE row and stays with the host, which
-then builds one HS_RESP_DTYPE descriptor per initiation it accepts.
+  peer_rows_build(table, n_ids)                   peer id -> row of the peer table
+  accept_batch / accept_host                      what follows noise.go:457 -- the comparison with lastTimestamp,
+                                                  the flood rule, the state update -- over consume_batch's rows
+                                                  and a table of HS_PEER_DTYPE rows; out come the HS_RESP_DTYPE
+                                                  descriptors respond_batch takes, :458-491
+The clock and the randomness are the caller's: the ephemeral private keys, the
+timestamp, the session indices and `now` are arguments, the first three of the
+responder's side as a pool of HS_TICKET_DTYPE rows.
 Curve25519, the HMAC / HKDF layer, the AEAD and the kernels live in
 libwgcsum.so (wgcs_x25519.h, wgcs_noise.h, noise_kernels.hip); nothing here
 computes.
@@ -31,9 +34,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (ERR_AUTH, ERR_LOW_ORDER, ERR_NO_HANDSHAKE, ERR_NO_PEER, HS_CONSUMED, HS_FINISHED, HS_INITIATED, HS_NONE,
-                   HS_PASS, HS_RESP_COOKIE, HS_RESPONDED, HS_START_COOKIE, HS_STATE_INITIATED, HS_STATE_ZEROED, PEER_NONE,
-                   PEER_RUNNING)
+from ._lib import (ERR_AUTH, ERR_BATCH_FULL, ERR_FLOOD, ERR_LOW_ORDER, ERR_NO_HANDSHAKE, ERR_NO_PEER, ERR_REPLAY,
+                   HS_ACCEPTED, HS_CONSUMED, HS_FINISHED, HS_INITIATED, HS_NONE, HS_PASS, HS_PEER_CONSUMED, HS_PEER_COOKIE,
+                   HS_PEER_SEEN, HS_PEER_ZEROED, HS_RESP_COOKIE, HS_RESPONDED, HS_START_COOKIE, HS_STATE_INITIATED,
+                   HS_STATE_ZEROED, PEER_NONE, PEER_RUNNING)
 from .cookie import _fixed, _status
 from .router import SESSION_SLOT_DTYPE
 from .transport import AEAD_KEY_DTYPE, AEAD_PKT_DTYPE, _rows
@@ -56,11 +60,18 @@ HS_START_DTYPE = np.dtype([("state_row", "<u4"), ("peer_row", "<u4"), ("local_in
                            ("recv_key", "<u4"), ("flags", "<u4"), ("timestamp", "u1", (12,)), ("pad0", "u1", (4,)),
                            ("ephemeral_private", "u1", (32,)), ("cookie", "u1", (16,)),
                            ("pad1", "u1", (8,))])  # wgcs_hs_start
+HS_PEER_DTYPE = np.dtype([("last_timestamp", "u1", (12,)), ("state", "<u4"), ("last_consumption_ns", "<i8"),
+                          ("flags", "<u4"), ("remote_index", "<u4"), ("claim", "<u4"), ("cookie", "u1", (16,)),
+                          ("pad", "u1", (12,))])  # wgcs_hs_peer
+HS_TICKET_DTYPE = np.dtype([("local_index", "<u4"), ("send_key", "<u4"), ("recv_key", "<u4"), ("pad", "<u4"),
+                            ("ephemeral_private", "u1", (32,))])  # wgcs_hs_ticket
+HS_CLAIM_NONE = 0xFFFFFFFF  # wgcs_hs_peer.claim outside a call
 RESPONSE_SIZE, RESPONSE_PITCH = 92, 96  # MessageResponseSize; a row of respond_batch's msgs
 INITIATION_SIZE, INITIATION_PITCH = 148, 160  # MessageInitiationSize; a row of initiate_batch's msgs
 FINISH_WORK_BYTES = 64  # finish_batch's scratch per row
 assert NOISE_RESPONDER_DTYPE.itemsize == 96 and PEER_KEY_DTYPE.itemsize == 72 and HS_INIT_DTYPE.itemsize == 128
 assert HS_RESP_DTYPE.itemsize == 80 and HS_STATE_DTYPE.itemsize == 128 and HS_START_DTYPE.itemsize == 96
+assert HS_PEER_DTYPE.itemsize == 64 and HS_TICKET_DTYPE.itemsize == 48
 
 __all__ = ["NOISE_RESPONDER_DTYPE", "PEER_KEY_DTYPE", "HS_INIT_DTYPE", "x25519", "responder_init", "peer_keys_build",
            "peer_keys_find", "consume_initiation", "create_initiation", "x25519_batch", "consume_batch", "HS_NONE",
@@ -68,7 +79,10 @@ __all__ = ["NOISE_RESPONDER_DTYPE", "PEER_KEY_DTYPE", "HS_INIT_DTYPE", "x25519",
            "HS_RESP_DTYPE", "RESPONSE_SIZE", "RESPONSE_PITCH", "create_response", "consume_response", "respond_batch",
            "HS_RESPONDED", "HS_RESP_COOKIE", "HS_STATE_DTYPE", "HS_START_DTYPE", "INITIATION_SIZE", "INITIATION_PITCH",
            "FINISH_WORK_BYTES", "initiate_batch", "finish_batch", "initiate_host", "finish_host", "HS_INITIATED",
-           "HS_FINISHED", "HS_START_COOKIE", "HS_STATE_ZEROED", "HS_STATE_INITIATED", "ERR_NO_HANDSHAKE"]
+           "HS_FINISHED", "HS_START_COOKIE", "HS_STATE_ZEROED", "HS_STATE_INITIATED", "ERR_NO_HANDSHAKE",
+           "HS_PEER_DTYPE", "HS_TICKET_DTYPE", "HS_CLAIM_NONE", "peer_rows_build", "accept_batch", "accept_host",
+           "HS_ACCEPTED", "ERR_FLOOD", "ERR_REPLAY", "ERR_BATCH_FULL", "HS_PEER_ZEROED", "HS_PEER_CONSUMED",
+           "HS_PEER_SEEN", "HS_PEER_COOKIE"]
 
 
 def _one(x, dtype: np.dtype, what: str) -> np.ndarray:
@@ -325,3 +339,58 @@ def finish_host(arena, pkts, types, gate, responder, slots, states, psk, keys, w
                                                    None if k is None else k.ctypes.data, n_peers,
                                                    ks.ctypes.data if len(ks) else None, len(ks), w.ctypes.data,
                                                    out.ctypes.data), "wgcs_handshake_finish_host")
+
+
+def peer_rows_build(table, n_ids: int) -> np.ndarray:
+    """wgcs_peer_rows_build: rows[id] (uint32) = the row of the PEER_KEY_DTYPE
+    table whose peer is id, PEER_NONE for an id no row has.  An id >= n_ids in
+    the table raises."""
+    t = np.ascontiguousarray(table, dtype=PEER_KEY_DTYPE).reshape(-1)
+    rows = np.zeros(n_ids, np.uint32)
+    _status(_lib.load().wgcs_peer_rows_build(t.ctypes.data if len(t) else None, len(t),
+                                             rows.ctypes.data if n_ids else None, n_ids), "wgcs_peer_rows_build")
+    return rows
+
+
+def accept_batch(dev, init, gate, now_ns: int, table, peer_rows, peers, tickets, resp, count, verdict, stream=None,
+                 n: int | None = None, n_ids: int | None = None, n_peers: int | None = None,
+                 n_tickets: int | None = None) -> None:
+    """Asynchronous wgcs_handshake_accept_batch between consume_batch and
+    respond_batch: `init` and `gate` are consume_batch's out and verdict, `table`
+    its PEER_KEY_DTYPE rows, `peer_rows` peer_rows_build's uint32 rows of it,
+    `peers` one HS_PEER_DTYPE row per table row, `tickets` HS_TICKET_DTYPE rows.
+    verdict[q] (int32) = gate[q] where that is not HS_CONSUMED, else HS_ACCEPTED,
+    ERR_NO_PEER, ERR_REPLAY, ERR_FLOOD or ERR_BATCH_FULL; resp (one
+    HS_RESP_DTYPE row per ticket), count (one uint32) and peers as the header
+    says.  Everything is on the device; now_ns is an int64 of the caller's
+    monotonic clock."""
+    s = getattr(stream, "cuda_stream", stream)
+    n = (0 if init is None else _rows(init, HS_INIT_DTYPE)) if n is None else n
+    n_ids = (0 if peer_rows is None else _rows(peer_rows, np.dtype("<u4"))) if n_ids is None else n_ids
+    n_peers = (0 if table is None else _rows(table, PEER_KEY_DTYPE)) if n_peers is None else n_peers
+    n_tickets = (0 if tickets is None else _rows(tickets, HS_TICKET_DTYPE)) if n_tickets is None else n_tickets
+    dev._check(dev.lib.wgcs_handshake_accept_batch(dev.h, _ptr(init), _ptr(gate), n, now_ns, _ptr(table), _ptr(peer_rows),
+                                                   n_ids, _ptr(peers), n_peers, _ptr(tickets), n_tickets, _ptr(resp),
+                                                   _ptr(count), _ptr(verdict), s))
+
+
+def accept_host(init, gate, now_ns: int, table, peer_rows, peers, tickets, resp, count, verdict) -> None:
+    """wgcs_handshake_accept_host: accept_batch on numpy arrays, in its passes.
+    `peers` (HS_PEER_DTYPE), `resp` (HS_RESP_DTYPE, one row per ticket), `count`
+    (one uint32) and `verdict` (int32) are written in place."""
+    i = np.ascontiguousarray(init, dtype=HS_INIT_DTYPE).reshape(-1)
+    g = np.ascontiguousarray(gate, dtype=np.int32).reshape(-1)
+    t = np.ascontiguousarray(table, dtype=PEER_KEY_DTYPE).reshape(-1)
+    pr = np.ascontiguousarray(peer_rows, dtype=np.uint32).reshape(-1)
+    tk = np.ascontiguousarray(tickets, dtype=HS_TICKET_DTYPE).reshape(-1)
+    ps, r = _host(peers, HS_PEER_DTYPE, "peers"), _host(resp, HS_RESP_DTYPE, "resp")
+    c, out = _host(count, np.uint32, "count"), _host(verdict, np.int32, "verdict")
+    n = len(i)
+    if len(g) != n or len(out) < n or len(ps) != len(t) or len(r) < len(tk) or len(c) < 1:
+        raise ValueError("gate and verdict hold one row per initiation, peers one per table row, resp one per ticket")
+    _status(_lib.load().wgcs_handshake_accept_host(i.ctypes.data if n else None, g.ctypes.data if n else None, n, now_ns,
+                                                   t.ctypes.data if len(t) else None, pr.ctypes.data if len(pr) else None,
+                                                   len(pr), ps.ctypes.data if len(ps) else None, len(t),
+                                                   tk.ctypes.data if len(tk) else None, len(tk),
+                                                   r.ctypes.data if len(tk) else None, c.ctypes.data,
+                                                   out.ctypes.data if n else None), "wgcs_handshake_accept_host")

@@ -1,13 +1,26 @@
-"""X25519 and handshake measurement (DESIGN.md §4.14, §4.15, §4.16): the
+"""X25519 and handshake measurement (DESIGN.md §4.14 to §4.17): the
 device-resident wgcs_x25519_batch, wgcs_handshake_consume_batch,
-wgcs_handshake_respond_batch, wgcs_handshake_initiate_batch and
-wgcs_handshake_finish_batch on one MI355X, beside the same scalar code on one
+wgcs_handshake_respond_batch, wgcs_handshake_initiate_batch,
+wgcs_handshake_finish_batch and wgcs_handshake_accept_batch on one MI355X, beside the same scalar code on one
 host core.
 
-  python -m wireguard_amd.noise_bench --mode x25519|consume|respond|initiate|finish
+  python -m wireguard_amd.noise_bench --mode x25519|consume|respond|initiate|finish|accept
                                       [--rows 65536 --peers 1024 --steps 20 --warmup 3]
 
 Workload:
+  accept    the consume workload below, and behind it
+           wgcs_handshake_accept_batch over consume's rows against a fresh table
+           of peer rows, with `--tickets` tickets; one JSON line for `rows` and
+           one for 1,024 rows.  The authentic messages come from 16 peers and
+           are tiled, so a batch is a flood of replayed authentic initiations:
+           16 winners, the rest replays and floods.  Timed: the accept call
+           alone (HIP events; a device copy restores the peer rows before every
+           call), the chain consume -> accept -> respond on one stream, and the
+           way without the call: consume, synchronise, read d_out and the
+           verdicts back, wgcs_handshake_accept_host on one core, upload the
+           descriptors, respond.  The two chains are timed by a host clock
+           around one call that ends in a synchronise, alternating; their
+           outputs are compared before anything is timed.
   initiate `rows` descriptors, every one of which runs the whole function: state
            row q and key rows 2q and 2q + 1, the peers in turn, a fresh ephemeral
            key, timestamp and index each, a cookie on every other one.
@@ -217,9 +230,162 @@ def make_finish(n: int, n_peers: int, distinct: int, seed: int = 20261024):
     return me, table, psk, all_states, arena, pkts, slots
 
 
+def run_accept(args, dev, torch) -> None:
+    """--mode accept: one JSON line per batch size (see the module docstring)."""
+    L = _lib.load()
+    stream = torch.cuda.current_stream()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
+
+    def pinned(nbytes):
+        return torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+
+    now, nt = 1_700_000_000_000_000_000, args.tickets
+    for n in dict.fromkeys((args.rows, min(args.rows, 1024))):
+        responder, table, arena, pkts, msgs, is_valid = make_consume(n, args.peers, args.valid, args.distinct)
+        n_peers = len(table)
+        peer_rows = noise.peer_rows_build(table, n_peers)
+        peers0 = np.zeros(n_peers, noise.HS_PEER_DTYPE)
+        peers0["claim"] = noise.HS_CLAIM_NONE
+        rng = np.random.default_rng(20261025)
+        tickets = np.zeros(nt, noise.HS_TICKET_DTYPE)
+        tickets["local_index"] = rng.integers(0, 2**32, nt, dtype=np.uint32)
+        tickets["send_key"], tickets["recv_key"] = 2 * np.arange(nt, dtype=np.uint32), 2 * np.arange(nt, dtype=np.uint32) + 1
+        tickets["ephemeral_private"] = rng.integers(0, 256, (nt, 32), dtype=np.uint8)
+        d_arena, d_pkts, d_responder, d_table = up(arena), up(pkts), up(responder), up(table)
+        d_rows, d_peers0, d_tickets = up(peer_rows), up(peers0), up(tickets)
+        d_peers = d_peers0.clone()
+        d_type = torch.ones(n, dtype=torch.int32, device="cuda")
+        d_consumed = torch.full((n,), -99, dtype=torch.int32, device="cuda")
+        d_verdict = torch.full((n,), -99, dtype=torch.int32, device="cuda")
+        d_init = torch.zeros(128 * n, dtype=torch.uint8, device="cuda")
+        d_resp = torch.zeros(80 * nt, dtype=torch.uint8, device="cuda")
+        d_count = torch.zeros(1, dtype=torch.int32, device="cuda")
+        d_keys = torch.zeros(48 * 2 * nt, dtype=torch.uint8, device="cuda")
+        d_msgs = torch.zeros(noise.RESPONSE_PITCH * nt, dtype=torch.uint8, device="cuda")
+        d_status = torch.full((nt,), -99, dtype=torch.int32, device="cuda")
+
+        def consume():
+            noise.consume_batch(dev, d_arena, d_pkts, d_type, None, d_responder, d_table, d_consumed, d_init,
+                                stream=stream, n=n, n_peers=n_peers)
+
+        def accept():
+            d_peers.copy_(d_peers0)  # the call commits what it accepts: every launch starts from the same table
+            noise.accept_batch(dev, d_init, d_consumed, now, d_table, d_rows, d_peers, d_tickets, d_resp, d_count,
+                               d_verdict, stream=stream, n=n, n_ids=n_peers, n_peers=n_peers, n_tickets=nt)
+
+        def respond(m=nt):
+            noise.respond_batch(dev, d_resp, d_init, None, d_table, None, d_keys, d_msgs, d_status, stream=stream, n=m,
+                                n_init=n, n_peers=n_peers, n_keys=2 * nt)
+
+        def device_chain():
+            consume(), accept(), respond()
+
+        # the parent's way: consume, synchronise, read the rows back, the tail on one host core, upload, respond
+        h_init, h_consumed, h_resp = pinned(128 * n), pinned(4 * n), pinned(80 * nt)
+        np_init, np_consumed = h_init.numpy().view(HS_INIT_DTYPE), h_consumed.numpy().view(np.int32)
+        np_resp = h_resp.numpy().view(noise.HS_RESP_DTYPE)
+        h_peers, h_count, h_verdict = peers0.copy(), np.zeros(1, np.uint32), np.zeros(n, np.int32)
+        tail_s = []
+
+        def host_tail():
+            h_peers[:] = peers0
+            t0 = time.perf_counter()
+            rc = L.wgcs_handshake_accept_host(np_init.ctypes.data, np_consumed.ctypes.data, n, now, table.ctypes.data,
+                                              peer_rows.ctypes.data, n_peers, h_peers.ctypes.data, n_peers,
+                                              tickets.ctypes.data, nt, np_resp.ctypes.data, h_count.ctypes.data,
+                                              h_verdict.ctypes.data)
+            tail_s.append(time.perf_counter() - t0)
+            assert rc == 0
+
+        def host_chain():
+            consume()
+            h_init.copy_(d_init, non_blocking=True)
+            h_consumed.copy_(d_consumed.view(torch.uint8), non_blocking=True)
+            stream.synchronize()
+            host_tail()
+            m = int(h_count[0])
+            if m:
+                d_resp[:80 * m].copy_(h_resp[:80 * m], non_blocking=True)
+                respond(m)
+
+        # both ways give the same bytes, and they are the host form's
+        device_chain()
+        torch.cuda.synchronize()
+        got = (d_verdict.cpu().numpy(), d_peers.cpu().numpy(), d_resp.cpu().numpy(), int(d_count.item()),
+               d_msgs.cpu().numpy(), d_keys.cpu().numpy(), d_status.cpu().numpy())
+        d_msgs.zero_(), d_keys.zero_(), d_status.fill_(-99)
+        host_chain()
+        torch.cuda.synchronize()
+        m = int(h_count[0])
+        assert np.array_equal(got[0], h_verdict), "device verdicts != host form"
+        assert got[1].tobytes() == h_peers.tobytes() and got[3] == m, "device peer rows / count != host form"
+        assert got[2].tobytes() == np_resp.tobytes(), "device descriptors != host form"
+        assert got[4][:noise.RESPONSE_PITCH * m].tobytes() == d_msgs.cpu().numpy()[:noise.RESPONSE_PITCH * m].tobytes(), "responses"
+        assert got[5].tobytes() == d_keys.cpu().numpy().tobytes(), "keys"
+        assert (got[6][:m] == noise.HS_RESPONDED).all() and (got[6][m:] == _lib.ERR_INVALID_ARG).all(), "status"
+        assert m == int((h_verdict == noise.HS_ACCEPTED).sum()) and m > 0
+
+        def events(fn):
+            for _ in range(args.warmup):
+                fn()
+            e0.record(stream)
+            for _ in range(args.steps):
+                fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / args.steps * 1e3
+
+        def wall(fn):
+            """us per call, each call ending in a synchronise: (median, min)"""
+            out = []
+            for k in range(args.warmup + args.steps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if k >= args.warmup:
+                    out.append((time.perf_counter() - t0) * 1e6)
+            return round(float(np.median(out)), 2), round(min(out), 2)
+
+        accept_us = events(accept)
+        restore_us = events(lambda: d_peers.copy_(d_peers0))
+        chain_events_us = events(device_chain)
+        consume_us = events(consume)
+        rounds = [(wall(device_chain), wall(host_chain)) for _ in range(3)]  # alternating, in one process
+        del tail_s[:]
+        for _ in range(5):
+            host_tail()
+        tail_us = float(np.median(tail_s)) * 1e6
+        verdicts = {str(k): int(v) for k, v in zip(*np.unique(h_verdict, return_counts=True))}
+        res = {
+            "metric": "handshake_accept_rows_per_s", "value": round(n / (accept_us * 1e-6)), "unit": "rows/s",
+            "us_per_launch": round(accept_us, 2), "steps": args.steps, "warmup": args.warmup,
+            "kernel": "hs_accept_claim_kernel + hs_accept_verdict_kernel + hs_accept_scan_kernel + hs_accept_commit_kernel",
+            "timing": "HIP events around K calls; each call is a device copy that restores the peer rows, then the four launches",
+            "peer_row_restore_us": round(restore_us, 2),
+            "workload": {"rows": n, "peers": n_peers, "calling_peers": min(INITIATORS, n_peers), "tickets": nt,
+                         "valid_fraction": round(float(is_valid.mean()), 4), "distinct_messages": min(args.distinct, n),
+                         "verdicts": verdicts, "now": "one value; every peer row starts fresh"},
+            "chain_consume_accept_respond": {
+                "device_events_us": round(chain_events_us, 2), "consume_alone_events_us": round(consume_us, 2),
+                "respond": f"{nt} descriptors, NULL gate, count not read",
+                "device_wall_us_median_min": [r[0] for r in rounds],
+                "parent_way_wall_us_median_min": [r[1] for r in rounds],
+                "parent_way": "consume, stream synchronise, d_out and verdicts to pinned memory, wgcs_handshake_accept_host on "
+                              "one core, upload of the descriptors written, respond over them",
+                "wall": "host clock around one call ending in a device synchronise; three rounds, the two ways alternating"},
+            "host_one_core": {"us_per_batch": round(tail_us, 2), "ns_per_row": round(tail_us * 1e3 / n, 2), "rows": n,
+                              "path": "wgcs_handshake_accept_host, one ctypes call for all rows"},
+        }
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--mode", choices=("x25519", "consume", "respond", "initiate", "finish"), required=True)
+    ap.add_argument("--mode", choices=("x25519", "consume", "respond", "initiate", "finish", "accept"), required=True)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", type=int, default=65536)
@@ -227,6 +393,7 @@ def main():
     ap.add_argument("--valid", type=float, default=0.5, help="fraction of authentic initiations (consume)")
     ap.add_argument("--distinct", type=int, default=1024, help="authentic messages made on the host and tiled")
     ap.add_argument("--host-rows", type=int, default=512, help="rows the one-core host path is timed over")
+    ap.add_argument("--tickets", type=int, default=64, help="responses the caller is ready to pay for (accept)")
     ap.add_argument("--no-openssl", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
@@ -241,6 +408,10 @@ def main():
         raise SystemExit("noise_bench: no GPU (this measurement does not fall back)")
     torch.cuda.set_device(args.device)
     dev = Device(args.device)
+    if args.mode == "accept":
+        run_accept(args, dev, torch)
+        dev.close()
+        return
     L = _lib.load()
     n = args.rows
     host_n = min(args.host_rows, n)
