@@ -988,8 +988,9 @@ int wgcs_handshake_screen_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgc
  * CreateMessageInitiation and ConsumeMessageResponse with its session keys --
  * runs here too, joined by a table of handshake states in device memory
  * (wgcs_handshake_initiate_batch and wgcs_handshake_finish_batch, the section
- * before the last).  What stays with the host is index allocation, lastSentHandshake
- * and the timers, keypair rotation and the consumption of cookie replies.
+ * before the last).  Keypair rotation runs on the stream too (the wgcs_keypairs
+ * calls of the last section).  What stays with the host is index allocation,
+ * lastSentHandshake and the timers, and the consumption of cookie replies.
  * Nothing here draws randomness or reads a clock. */
 
 /* curve25519.X25519 (RFC 7748 section 5; noise_helpers.go:93-105): the scalar is
@@ -1176,8 +1177,9 @@ int wgcs_handshake_respond_batch(wgcs_ctx *ctx, const wgcs_hs_resp *d_resp, uint
  * and wgcs_handshake_finish_batch consumes it, so neither the ephemeral secret
  * nor a transport key of the initiator crosses to the host.  The host keeps
  * what the reference keeps under locks and clocks: sessions.NewIndex,
- * lastSentHandshake and the timers, keypair rotation, and the consumption of
- * cookie replies (wgcs_cookie_consume_reply). */
+ * lastSentHandshake and the timers, and the consumption of cookie replies
+ * (wgcs_cookie_consume_reply); keypair rotation follows on the stream
+ * (wgcs_keypairs_begin_initiator_batch, the last section). */
 
 #define WGCS_HS_STATE_ZEROED 0    /* handshakeZeroed */
 #define WGCS_HS_STATE_INITIATED 1 /* handshakeInitiationCreated */
@@ -1403,6 +1405,163 @@ int wgcs_handshake_accept_host(const wgcs_hs_init *init, const int32_t *gate, ui
                                const wgcs_peer_key *table, const uint32_t *peer_rows, uint32_t n_ids,
                                wgcs_hs_peer *peers, uint32_t n_peers, const wgcs_hs_ticket *tickets,
                                uint32_t n_tickets, wgcs_hs_resp *resp, uint32_t *count, int32_t *verdict);
+
+/* ---- keypair rotation: begin-session and first-receive (device/noise.go:664-754,
+ * device/sessions.go:70-82, device/receive.go:418-429) ----
+ * What puts the keys of a finished handshake to use, between the handshake
+ * batches (respond, finish) and the transport batches on one stream: the tail
+ * of BeginSymmetricSession -- sessions.AddKeypair, the rotation of previous /
+ * current / next with its DeleteSession calls, the initiator's new send key --
+ * and ReceivedWithNewKeypair, which promotes the responder's next keypair on
+ * the first valid transport packet under it.  Both work on one table of
+ * wgcs_keypairs rows in device memory, one per row of the peer table, and on
+ * the two slot tables the per-packet path reads: d_slots (receiver index -> key
+ * row, wgcs_recv_classify_batch) and d_peer_keys (peer id -> send-key row,
+ * wgcs_send_assign_batch).  No slot is inserted or removed: a call only
+ * overwrites the key of a slot that exists, so a probe that runs beside it is
+ * never broken.  The host registers ahead of time, when it allocates them:
+ * every index of a ticket or a wgcs_hs_start goes into d_slots, and every peer
+ * id into d_peer_keys, with the key WGCS_SESSION_NO_KEYPAIR.  That key is past
+ * every key table (n_keys <= 2^24), so classify hands it on and open, replay,
+ * send-assign and the write builder refuse it without touching a row.
+ * The host keeps index allocation, the timers, SetEndpointFromPacket and
+ * SendStagedPackets (from d_rotated), keypair expiry by created_ns, and the
+ * reclaiming of tombstoned slots when it rebuilds a table.
+ *
+ * DeleteSession(x) for a set entry x: the slot of x.local_index in d_slots
+ * gets key WGCS_SESSION_NO_KEYPAIR, the 48-byte rows d_keys[x.send_key] and
+ * d_keys[x.recv_key] are zeroed (the reference cannot erase key material,
+ * keypair.go:12-17), and d_key_peer[x.send_key] = d_key_peer[x.recv_key] =
+ * WGCS_PEER_NONE.  For a nil entry it does nothing.  A key row of x at or past
+ * n_keys, or an index without a slot, is skipped.  Zeroing a replay filter and
+ * a send nonce stays with the caller when it hands a key row out again. */
+
+#define WGCS_SESSION_NO_KEYPAIR 0xFFFFFFFEu /* a wgcs_session_slot key: the index is taken (NewIndex) but has
+                                               no keypair yet, or its keypair was deleted: Get finds keypair == nil */
+#define WGCS_KEYPAIR_SET 0x1u        /* wgcs_keypair_ref.flags bit 0: the entry holds a keypair; else it is nil and all zero */
+#define WGCS_KEYPAIR_INITIATOR 0x2u  /* bit 1: keypair.isInitiator */
+#define WGCS_HS_BEGUN 8              /* the keypair is installed and its peer's three entries are rotated */
+
+#pragma pack(push, 4)
+typedef struct wgcs_keypair_ref {  /* 24 B */
+  uint32_t send_key, recv_key;     /* rows of the wgcs_aead_key table (and of d_send_nonce / d_filters) */
+  uint32_t local_index;            /* keypair.localIndex */
+  uint32_t flags;
+  int64_t created_ns;              /* keypair.createdAt on the caller's clock; only written here, read by the host */
+} wgcs_keypair_ref;
+typedef struct wgcs_keypairs {     /* 80 B: row r belongs to d_table[r] */
+  wgcs_keypair_ref previous, current, next;
+  uint32_t claim;                  /* 0xFFFFFFFF, or the lowest candidate row of the received call in flight */
+  uint32_t pad;
+} wgcs_keypairs;
+#pragma pack(pop)
+
+/* The tail of BeginSymmetricSession (noise.go:664-722) for the handshakes a
+ * batch completed, a few ordinary launches, asynchronous on stream (NULL: the
+ * context's), n <= 2^24, n_peers <= 2^24, n == 0 a no-op; no clock read.
+ * The responder's form runs behind wgcs_handshake_respond_batch: descriptor j
+ * is d_resp[j] as accept wrote it and respond consumed it, taken iff
+ * d_gate[j] == WGCS_HS_RESPONDED (d_gate is respond's d_status and may not be
+ * d_status); its peer_row, local_index, send_key and recv_key are read, its
+ * secret fields are not.  The initiator's form runs behind
+ * wgcs_handshake_finish_batch: row q of the receive batch is taken iff
+ * d_gate[q] == WGCS_HS_FINISHED (finish's d_verdict); the lane reads LE32
+ * msg[8:12] in the aligned words that hold it, finds the state row through
+ * d_hs_slots (finish's d_slots) and takes peer_row, local_index, send_key and
+ * recv_key from that row, which finish left in place; d_states is only read.
+ * Descriptor j, in this order:
+ *   not taken                                             d_status[j] = WGCS_HS_NONE; nothing else read
+ *   initiator: the index is not in d_hs_slots, its state
+ *   row >= n_states, or that row's local_index differs    WGCS_ERR_NO_HANDSHAKE
+ *   peer_row >= n_peers, a key row >= n_keys, or
+ *   send_key == recv_key                                  WGCS_ERR_INVALID_ARG; nothing written
+ *   local_index has no slot in d_slots, or its slot's
+ *   key is not WGCS_SESSION_NO_KEYPAIR                    WGCS_ERR_NO_HANDSHAKE; nothing written
+ *   otherwise                                             WGCS_HS_BEGUN
+ * For WGCS_HS_BEGUN, with new = {send_key, recv_key, local_index,
+ * WGCS_KEYPAIR_SET | WGCS_KEYPAIR_INITIATOR for the initiator's form, now_ns}:
+ * the slot of local_index gets key recv_key (AddKeypair), d_key_peer[send_key]
+ * = d_key_peer[recv_key] = d_table[peer_row].peer, and row peer_row of d_kp
+ * rotates as noise.go:700-721:
+ *   initiator, next set    next = nil, previous = old next, DeleteSession(old current),
+ *                          DeleteSession(old previous), current = new
+ *   initiator otherwise    previous = old current, DeleteSession(old previous), current = new
+ *   responder              next = new, DeleteSession(old next), previous = nil,
+ *                          DeleteSession(old previous); current is untouched
+ * Whenever current changes, the slot of d_table[peer_row].peer in d_peer_keys
+ * gets key current.send_key; a peer id with no slot there is left alone.
+ * The descriptors of one peer are applied in descriptor order, as sequential
+ * calls would be: the taken descriptors are grouped by peer_row in key order
+ * and one lane walks each peer's run.  Two taken descriptors of different
+ * peers that name one local_index or one key row are the caller's error, and
+ * the outcome is then unspecified.  d_work is wgcs_keyorder_work_bytes(n) of
+ * the caller's device memory, 16-byte aligned.  n_slots, n_peer_slots and
+ * n_hs_slots are 0 or a power of two; d_pkts is 8-byte aligned, everything
+ * else 4-byte aligned.  WGCS_ERR_INVALID_ARG, nothing written, for a NULL
+ * pointer that is needed, d_status == d_gate, a count over its bound, a
+ * misaligned pointer or a workspace that is too small. */
+int wgcs_keypairs_begin_responder_batch(wgcs_ctx *ctx, const wgcs_hs_resp *d_resp, const int32_t *d_gate, uint32_t n,
+                                        int64_t now_ns, const wgcs_peer_key *d_table, uint32_t n_peers,
+                                        wgcs_keypairs *d_kp, wgcs_session_slot *d_slots, uint32_t n_slots,
+                                        wgcs_session_slot *d_peer_keys, uint32_t n_peer_slots, wgcs_aead_key *d_keys,
+                                        uint32_t *d_key_peer, uint32_t n_keys, int32_t *d_status, void *d_work,
+                                        size_t work_bytes, void *stream);
+int wgcs_keypairs_begin_initiator_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgcs_aead_pkt *d_pkts,
+                                        const int32_t *d_gate, uint32_t n, int64_t now_ns,
+                                        const wgcs_session_slot *d_hs_slots, uint32_t n_hs_slots,
+                                        const wgcs_hs_state *d_states, uint32_t n_states, const wgcs_peer_key *d_table,
+                                        uint32_t n_peers, wgcs_keypairs *d_kp, wgcs_session_slot *d_slots,
+                                        uint32_t n_slots, wgcs_session_slot *d_peer_keys, uint32_t n_peer_slots,
+                                        wgcs_aead_key *d_keys, uint32_t *d_key_peer, uint32_t n_keys, int32_t *d_status,
+                                        void *d_work, size_t work_bytes, void *stream);
+
+/* ReceivedWithNewKeypair (noise.go:725-754) as receive.go:418-429 calls it,
+ * behind wgcs_replay_batch on the receive chain's stream: two ordinary
+ * launches, asynchronous on stream, n <= 2^28, n == 0 a no-op.  Row i takes
+ * part iff d_pkts[i].key < n_keys and d_verdict[i] >= 0 or ==
+ * WGCS_ERR_PACKET_TOO_SHORT (decrypted and past the filter; WGCS_ERR_AUTH and
+ * WGCS_ERR_REPLAY rows do not), its peer id d_key_peer[key] is < n_ids, and
+ * that id's row d_peer_rows[id] is neither WGCS_PEER_NONE nor >= n_peers.  It is
+ * a candidate iff that row's next is set and next.recv_key == key.  Of one
+ * peer's candidates the lowest row wins, whatever the timing: the first launch
+ * takes the minimum of the candidates' row numbers in the row's claim, the
+ * second commits the rows that hold their claim and leaves claim = 0xFFFFFFFF,
+ * as it must be before the call.  The winning row: d_rotated[i] = 1,
+ * DeleteSession(old previous), previous = current, current = next, next = nil,
+ * and the peer id's slot in d_peer_keys gets current.send_key, so a
+ * wgcs_send_assign_batch that follows on the stream seals under the promoted
+ * key.  Every other row of the n gets d_rotated[i] = 0 and changes nothing.
+ * d_pkts, d_verdict and d_peer_rows are only read; d_key_peer is read, and
+ * written by DeleteSession alone.  d_pkts is 8-byte aligned, everything else
+ * 4-byte aligned; n_slots and n_peer_slots are 0 or a power of two. */
+int wgcs_keypairs_received_batch(wgcs_ctx *ctx, const wgcs_aead_pkt *d_pkts, const int32_t *d_verdict, uint32_t n,
+                                 uint32_t *d_key_peer, uint32_t n_keys, const uint32_t *d_peer_rows, uint32_t n_ids,
+                                 wgcs_keypairs *d_kp, uint32_t n_peers, wgcs_session_slot *d_slots, uint32_t n_slots,
+                                 wgcs_session_slot *d_peer_keys, uint32_t n_peer_slots, wgcs_aead_key *d_keys,
+                                 uint32_t *d_rotated, void *stream);
+
+/* The three on host memory, no context and no device: the same row functions,
+ * taken in row order (the received form in the same two passes), with the same
+ * tables and the same outputs.  WGCS_ERR_INVALID_ARG for a NULL pointer the
+ * device form refuses, a count over its bound or a slot count that is not 0 or
+ * a power of two; n == 0 a no-op. */
+int wgcs_keypairs_begin_responder_host(const wgcs_hs_resp *resp, const int32_t *gate, uint32_t n, int64_t now_ns,
+                                       const wgcs_peer_key *table, uint32_t n_peers, wgcs_keypairs *kp,
+                                       wgcs_session_slot *slots, uint32_t n_slots, wgcs_session_slot *peer_keys,
+                                       uint32_t n_peer_slots, wgcs_aead_key *keys, uint32_t *key_peer, uint32_t n_keys,
+                                       int32_t *status);
+int wgcs_keypairs_begin_initiator_host(const uint8_t *arena, const wgcs_aead_pkt *pkts, const int32_t *gate,
+                                       uint32_t n, int64_t now_ns, const wgcs_session_slot *hs_slots,
+                                       uint32_t n_hs_slots, const wgcs_hs_state *states, uint32_t n_states,
+                                       const wgcs_peer_key *table, uint32_t n_peers, wgcs_keypairs *kp,
+                                       wgcs_session_slot *slots, uint32_t n_slots, wgcs_session_slot *peer_keys,
+                                       uint32_t n_peer_slots, wgcs_aead_key *keys, uint32_t *key_peer, uint32_t n_keys,
+                                       int32_t *status);
+int wgcs_keypairs_received_host(const wgcs_aead_pkt *pkts, const int32_t *verdict, uint32_t n, uint32_t *key_peer,
+                                uint32_t n_keys, const uint32_t *peer_rows, uint32_t n_ids, wgcs_keypairs *kp,
+                                uint32_t n_peers, wgcs_session_slot *slots, uint32_t n_slots,
+                                wgcs_session_slot *peer_keys, uint32_t n_peer_slots, wgcs_aead_key *keys,
+                                uint32_t *rotated);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,9 @@ HS_STATE_ZEROED, HS_STATE_INITIATED = 0, 1  # wgcs_hs_state.state
 HS_ACCEPTED = 7  # wgcs_handshake_accept_batch's
 HS_PEER_ZEROED, HS_PEER_CONSUMED = 0, 1  # wgcs_hs_peer.state
 HS_PEER_SEEN, HS_PEER_COOKIE = 0x1, 0x2  # wgcs_hs_peer.flags: the peer has consumed before; cookie[] is valid
+HS_BEGUN = 8  # wgcs_keypairs_begin_*_batch's
+SESSION_NO_KEYPAIR = 0xFFFFFFFE  # a wgcs_session_slot key: the index is taken, its keypair is nil
+KEYPAIR_SET, KEYPAIR_INITIATOR = 0x1, 0x2  # wgcs_keypair_ref.flags
 PEER_RUNNING = 0x1  # wgcs_peer_key.flags: peer.isRunning
 GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
 
@@ -230,6 +233,16 @@ def load() -> C.CDLL:
         "wgcs_peer_rows_build": ([vp, u32, vp, u32], i32),
         "wgcs_handshake_accept_batch": ([vp, vp, vp, u32, C.c_int64, vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp], i32),
         "wgcs_handshake_accept_host": ([vp, vp, u32, C.c_int64, vp, vp, u32, vp, u32, vp, u32, vp, vp, vp], i32),
+        "wgcs_keypairs_begin_responder_batch": ([vp, vp, vp, u32, C.c_int64, vp, u32, vp, vp, u32, vp, u32, vp, vp, u32,
+                                                 vp, vp, sz, vp], i32),
+        "wgcs_keypairs_begin_initiator_batch": ([vp, vp, vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, u32, vp, vp, u32,
+                                                 vp, u32, vp, vp, u32, vp, vp, sz, vp], i32),
+        "wgcs_keypairs_received_batch": ([vp, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp, vp], i32),
+        "wgcs_keypairs_begin_responder_host": ([vp, vp, u32, C.c_int64, vp, u32, vp, vp, u32, vp, u32, vp, vp, u32, vp],
+                                               i32),
+        "wgcs_keypairs_begin_initiator_host": ([vp, vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, u32, vp, vp, u32, vp,
+                                                u32, vp, vp, u32, vp], i32),
+        "wgcs_keypairs_received_host": ([vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

@@ -130,4 +130,26 @@ hipError_t launch_hs_accept(const wgcs_hs_init* init, const int32_t* gate, uint3
                             uint32_t n_peers, const wgcs_hs_ticket* tickets, uint32_t n_tickets, wgcs_hs_resp* resp,
                             uint32_t* count, int32_t* verdict, uint32_t* block_winners, hipStream_t s);
 
+// Keypair rotation (keypairs_kernels.hip, the row functions of wgcs_keypairs.h).  The two begin
+// forms group their descriptors by peer row on a carved workspace (wgcs_keyorder.h) and let one
+// lane walk each peer's run; received is two launches, claim and commit.
+hipError_t launch_keypairs_begin_responder(const KeyOrder& ko, const wgcs_hs_resp* resp, const int32_t* gate,
+                                           uint32_t n, int64_t now, const wgcs_peer_key* table, uint32_t n_peers,
+                                           wgcs_keypairs* kp, wgcs_session_slot* slots, uint32_t n_slots,
+                                           wgcs_session_slot* peer_keys, uint32_t n_peer_slots, wgcs_aead_key* keys,
+                                           uint32_t* key_peer, uint32_t n_keys, int32_t* status, hipStream_t s);
+hipError_t launch_keypairs_begin_initiator(const KeyOrder& ko, const uint8_t* arena, const wgcs_aead_pkt* pkts,
+                                           const int32_t* gate, uint32_t n, int64_t now,
+                                           const wgcs_session_slot* hs_slots, uint32_t n_hs_slots,
+                                           const wgcs_hs_state* states, uint32_t n_states, const wgcs_peer_key* table,
+                                           uint32_t n_peers, wgcs_keypairs* kp, wgcs_session_slot* slots,
+                                           uint32_t n_slots, wgcs_session_slot* peer_keys, uint32_t n_peer_slots,
+                                           wgcs_aead_key* keys, uint32_t* key_peer, uint32_t n_keys, int32_t* status,
+                                           hipStream_t s);
+hipError_t launch_keypairs_received(const wgcs_aead_pkt* pkts, const int32_t* verdict, uint32_t n, uint32_t* key_peer,
+                                    uint32_t n_keys, const uint32_t* peer_rows, uint32_t n_ids, wgcs_keypairs* kp,
+                                    uint32_t n_peers, wgcs_session_slot* slots, uint32_t n_slots,
+                                    wgcs_session_slot* peer_keys, uint32_t n_peer_slots, wgcs_aead_key* keys,
+                                    uint32_t* rotated, hipStream_t s);
+
 }  // namespace wgcs
