@@ -1177,9 +1177,11 @@ int wgcs_handshake_respond_batch(wgcs_ctx *ctx, const wgcs_hs_resp *d_resp, uint
  * and wgcs_handshake_finish_batch consumes it, so neither the ephemeral secret
  * nor a transport key of the initiator crosses to the host.  The host keeps
  * what the reference keeps under locks and clocks: sessions.NewIndex,
- * lastSentHandshake and the timers, and the consumption of cookie replies
+ * the timers, and the consumption of cookie replies
  * (wgcs_cookie_consume_reply); keypair rotation follows on the stream
- * (wgcs_keypairs_begin_initiator_batch, the last section). */
+ * (wgcs_keypairs_begin_initiator_batch), and lastSentHandshake with the
+ * decision who needs a handshake is wgcs_rekey_start_batch's (the last
+ * section), which writes d_start in device memory. */
 
 #define WGCS_HS_STATE_ZEROED 0    /* handshakeZeroed */
 #define WGCS_HS_STATE_INITIATED 1 /* handshakeInitiationCreated */
@@ -1308,8 +1310,8 @@ int wgcs_handshake_finish_host(const uint8_t *arena, const wgcs_aead_pkt *pkts, 
  * array of wgcs_hs_resp descriptors comes out that respond takes as it is.  No
  * clock is read and no randomness drawn: the caller passes now, and a pool of
  * tickets (session index, ephemeral private key, two key rows), one per
- * response it is ready to pay for.  The host keeps lastSentHandshake, the
- * timers, SetEndpointFromPacket from the verdict rows and the index allocation
+ * response it is ready to pay for.  The host keeps the timers (lastSentHandshake
+ * is wgcs_rekey_responded_batch's), SetEndpointFromPacket from the verdict rows and the index allocation
  * behind the tickets.  The initiator's wgcs_hs_state table is not touched. */
 
 #define WGCS_HS_ACCEPTED 7     /* the initiation won its peer's handshake: its descriptor is written */
@@ -1425,8 +1427,9 @@ int wgcs_handshake_accept_host(const wgcs_hs_init *init, const int32_t *gate, ui
  * every key table (n_keys <= 2^24), so classify hands it on and open, replay,
  * send-assign and the write builder refuse it without touching a row.
  * The host keeps index allocation, the timers, SetEndpointFromPacket and
- * SendStagedPackets (from d_rotated), keypair expiry by created_ns, and the
- * reclaiming of tombstoned slots when it rebuilds a table.
+ * SendStagedPackets (from d_rotated), and the reclaiming of tombstoned slots
+ * when it rebuilds a table.  Keypair expiry by created_ns is the next
+ * section's (wgcs_rekey_recv_gate_batch, wgcs_rekey_send_gate_batch).
  *
  * DeleteSession(x) for a set entry x: the slot of x.local_index in d_slots
  * gets key WGCS_SESSION_NO_KEYPAIR, the 48-byte rows d_keys[x.send_key] and
@@ -1447,7 +1450,7 @@ typedef struct wgcs_keypair_ref {  /* 24 B */
   uint32_t send_key, recv_key;     /* rows of the wgcs_aead_key table (and of d_send_nonce / d_filters) */
   uint32_t local_index;            /* keypair.localIndex */
   uint32_t flags;
-  int64_t created_ns;              /* keypair.createdAt on the caller's clock; only written here, read by the host */
+  int64_t created_ns;              /* keypair.createdAt on the caller's clock; written here, read by the wgcs_rekey_* calls */
 } wgcs_keypair_ref;
 typedef struct wgcs_keypairs {     /* 80 B: row r belongs to d_table[r] */
   wgcs_keypair_ref previous, current, next;
@@ -1562,6 +1565,200 @@ int wgcs_keypairs_received_host(const wgcs_aead_pkt *pkts, const int32_t *verdic
                                 uint32_t n_peers, wgcs_session_slot *slots, uint32_t n_slots,
                                 wgcs_session_slot *peer_keys, uint32_t n_peer_slots, wgcs_aead_key *keys,
                                 uint32_t *rotated);
+
+/* ---- keypair expiry, the rekey rules and the start of a handshake
+ * (device/receive.go:80-91, :162-170, device/send.go:84-100, :131-133, :213-227,
+ * :368-374, device/constants.go:12-30) ----
+ * What looks at a keypair's age and at its send nonce, and what asks for a new
+ * handshake, on the streams of the two transport chains and the handshake
+ * batches: a gate in each chain that refuses a packet under a keypair past
+ * RejectAfterTime or RejectAfterMessages, keepKeyFreshSending and
+ * keepKeyFreshReceiving behind them, and a start call that turns the wishes
+ * they left into wgcs_hs_start descriptors in device memory, which
+ * wgcs_handshake_initiate_batch takes as they are.  A session that ages out on
+ * the device is renewed on the device: gate -> start -> initiate -> (peer)
+ * consume -> accept -> respond -> begin -> finish -> begin, and the next send
+ * batch seals under the new key, with no synchronisation between them.
+ *
+ * The state is one wgcs_rekey row beside every wgcs_keypairs row.  A lane finds
+ * its peer as wgcs_keypairs_received_batch does: peer id -> d_peer_rows[id]
+ * (wgcs_peer_rows_build); an id >= n_ids, a row that is WGCS_PEER_NONE or one
+ * >= n_peers is "no row".  All clock arithmetic is now_ns - x in signed 64
+ * bits; the caller keeps |values| < 2^62.  A clock that went back fires no time
+ * rule, and in the start call it counts as "within the timeout".  One clock
+ * value serves a whole call, where the reference reads the clock per packet.
+ *
+ * The host keeps: filling tickets (NewIndex, newPrivateKey, tai64n.Now);
+ * sending the d_msgs rows that d_start_peer names; handshakeAttempts and the
+ * retry timers (d_reasons tells a retry, WGCS_REKEY_WANT_HOST alone, from a
+ * fresh request); timersHandshakeComplete, including clearing
+ * WGCS_REKEY_LAST_MINUTE by a stream-ordered write when it handles a
+ * WGCS_HS_BEGUN or d_rotated row -- until then the flag can only suppress a
+ * request that a keypair seconds old could not raise; cookie ageing
+ * (CookieRefreshTime) behind the WGCS_HS_PEER_COOKIE bit; expiredZeroOutKeys.
+ *
+ * The six calls share their conventions: asynchronous on stream (NULL: the
+ * context's), ordinary launches in blocks of 256, no clock read, no randomness
+ * drawn, aligned 4-byte or 8-byte accesses only, n == 0 a no-op.
+ * WGCS_ERR_INVALID_ARG, nothing written, for a NULL pointer that is needed, a
+ * count over its bound or a misaligned pointer: d_pkts, d_groups, d_send_nonce
+ * and d_rekey are 8-byte aligned, d_work 16-byte, everything else 4-byte. */
+
+#define WGCS_REJECT_AFTER_TIME_NS 180000000000ll /* RejectAfterTime, constants.go:26 */
+#define WGCS_REKEY_AFTER_TIME_NS 120000000000ll  /* RekeyAfterTime, :15 */
+#define WGCS_REKEY_TIMEOUT_NS 5000000000ll       /* RekeyTimeout, :18 */
+#define WGCS_KEEPALIVE_TIMEOUT_NS 10000000000ll  /* KeepaliveTimeout, :30 */
+#define WGCS_REKEY_AFTER_MESSAGES (1ull << 60)   /* RekeyAfterMessages, :12 */
+#define WGCS_SESSION_EXPIRED 0xFFFFFFFDu /* a wgcs_aead_pkt key: the keypair is past RejectAfterTime.  Past every
+                                            key table, so open refuses it with nothing read and replay, source and
+                                            the write builder pass it by */
+#define WGCS_ERR_KEY_EXPIRED (-26)   /* no current keypair, or it is past RejectAfterMessages / RejectAfterTime  send.go:369-371 */
+#define WGCS_ERR_REKEY_TIMEOUT (-27) /* within RekeyTimeout of lastSentHandshake  send.go:89-98 */
+#define WGCS_HS_STARTED 9            /* a wgcs_hs_start descriptor is written for the peer */
+
+#define WGCS_REKEY_LAST_MINUTE 0x1u /* wgcs_rekey.flags bit 0: timers.sentLastMinuteHandshake */
+
+/* wgcs_rekey.want: the reasons a handshake is wanted */
+#define WGCS_REKEY_WANT_NO_KEYPAIR 0x01u      /* send.go:369 */
+#define WGCS_REKEY_WANT_REJECT_MESSAGES 0x02u /* :370, :385-390 with :419-420 */
+#define WGCS_REKEY_WANT_REJECT_TIME 0x04u     /* :371 */
+#define WGCS_REKEY_WANT_REKEY_MESSAGES 0x08u  /* :223 */
+#define WGCS_REKEY_WANT_REKEY_TIME 0x10u      /* :224 */
+#define WGCS_REKEY_WANT_LAST_MINUTE 0x20u     /* receive.go:85-89 */
+#define WGCS_REKEY_WANT_HOST 0x40u            /* the host's own timers (expiredNewHandshake, expiredResendHandshake),
+                                                 set by a stream-ordered write */
+
+typedef struct wgcs_rekey { /* 16 B, 8-byte aligned: row r belongs to d_table[r] */
+  int64_t last_sent_ns;     /* handshake.lastSentHandshake on the caller's monotonic clock; the host
+                               initialises it to now - (RekeyTimeout + 1 s), peer.go:180 */
+  uint32_t want;            /* WGCS_REKEY_WANT_*, OR-ed in by the calls below; the start call clears it */
+  uint32_t flags;           /* WGCS_REKEY_LAST_MINUTE */
+} wgcs_rekey;
+
+/* receive.go:162-170, one launch between wgcs_recv_classify_batch and
+ * wgcs_aead_open_batch.  Row i takes part iff d_pkts[i].key < n_keys, its peer
+ * id d_key_peer[key] has a row, and one of that row's current, previous, next
+ * (in that order) is set with recv_key == key.  If now_ns - created_ns of that
+ * entry > WGCS_REJECT_AFTER_TIME_NS (Before is strict: equality passes),
+ * d_pkts[i].key = WGCS_SESSION_EXPIRED.  Nothing else is written; every other
+ * row is untouched.  n <= 2^28. */
+int wgcs_rekey_recv_gate_batch(wgcs_ctx *ctx, wgcs_aead_pkt *d_pkts, uint32_t n, int64_t now_ns,
+                               const uint32_t *d_key_peer, uint32_t n_keys, const uint32_t *d_peer_rows,
+                               uint32_t n_ids, const wgcs_keypairs *d_kp, uint32_t n_peers, void *stream);
+
+/* send.go:368-374, one launch between wgcs_route_dst_batch and
+ * wgcs_send_assign_batch.  Job j is taken by send-assign's own rule
+ * (d_status_in[j] == 0, 1 <= d_count[j] <= max_segs, peer id
+ * d_peer[j * max_segs]) if that peer has a row.  With current of that row:
+ *   current is nil                            d_status_out[j] = WGCS_ERR_KEY_EXPIRED, want |= NO_KEYPAIR
+ *   d_send_nonce[current.send_key] >= limit   WGCS_ERR_KEY_EXPIRED, want |= REJECT_MESSAGES  } both bits if
+ *   now_ns - created_ns >= REJECT_AFTER_TIME  WGCS_ERR_KEY_EXPIRED, want |= REJECT_TIME      } both hold
+ * Otherwise, for a current.send_key >= n_keys and for every job not taken,
+ * d_status_out[j] = d_status_in[j].  d_status_out may be d_status_in; it is
+ * what send-assign then reads as d_status, so a refused job stays staged with
+ * the caller.  want is written by atomicOr; d_kp and d_send_nonce are only
+ * read.  The rule of :370 is applied per batch and not per SendStagedPackets
+ * call.  n_jobs * max_segs <= 2^28. */
+int wgcs_rekey_send_gate_batch(wgcs_ctx *ctx, const uint32_t *d_peer, const int32_t *d_count,
+                               const int32_t *d_status_in, uint32_t n_jobs, uint32_t max_segs, int64_t now_ns,
+                               const uint32_t *d_peer_rows, uint32_t n_ids, const wgcs_keypairs *d_kp,
+                               uint32_t n_peers, const uint64_t *d_send_nonce, uint32_t n_keys, uint64_t limit,
+                               wgcs_rekey *d_rekey, int32_t *d_status_out, void *stream);
+
+/* keepKeyFreshSending (send.go:213-227, called at :523) and the goto top of
+ * :419-420, one launch behind wgcs_send_assign_batch over its outputs; Send is
+ * taken to have succeeded.  d_status is the gate's d_status_out.  Job j with
+ * status 0, a valid count, a peer row and a set current, with nonce =
+ * d_send_nonce[current.send_key] as send-assign left it (a send_key >= n_keys
+ * has none, and no nonce rule fires):
+ *   kept (d_job_key[j] != 0xFFFFFFFF)   nonce > WGCS_REKEY_AFTER_MESSAGES -> want |= REKEY_MESSAGES;
+ *                                       current is initiator and now_ns - created_ns >
+ *                                       WGCS_REKEY_AFTER_TIME_NS -> want |= REKEY_TIME
+ *   dropped                             nonce >= limit -> want |= REJECT_MESSAGES
+ * Nothing but want is written. */
+int wgcs_rekey_sent_batch(wgcs_ctx *ctx, const uint32_t *d_peer, const int32_t *d_count, const int32_t *d_status,
+                          const uint32_t *d_job_key, uint32_t n_jobs, uint32_t max_segs, int64_t now_ns,
+                          const uint32_t *d_peer_rows, uint32_t n_ids, const wgcs_keypairs *d_kp, uint32_t n_peers,
+                          const uint64_t *d_send_nonce, uint32_t n_keys, uint64_t limit, wgcs_rekey *d_rekey,
+                          void *stream);
+
+/* keepKeyFreshReceiving (receive.go:80-91, called at :486-488), one launch
+ * behind wgcs_write_build_batch over its n_batches * calls_per_batch rows of
+ * d_groups (<= 2^28).  A row with tail >= 0 whose peer has a row: if current
+ * is set and initiator and now_ns - created_ns > WGCS_REJECT_AFTER_TIME_NS -
+ * WGCS_KEEPALIVE_TIMEOUT_NS - WGCS_REKEY_TIMEOUT_NS, then old = atomicOr(&flags,
+ * WGCS_REKEY_LAST_MINUTE), and want |= LAST_MINUTE if the bit was clear in
+ * old.  There is no per-row output, so the tables are the same whichever
+ * group of a peer gets there first. */
+int wgcs_rekey_received_batch(wgcs_ctx *ctx, const wgcs_write_group *d_groups, uint32_t n_batches,
+                              uint32_t calls_per_batch, int64_t now_ns, const uint32_t *d_peer_rows, uint32_t n_ids,
+                              const wgcs_keypairs *d_kp, uint32_t n_peers, wgcs_rekey *d_rekey, void *stream);
+
+/* SendHandshakeResponse's lastSentHandshake (send.go:131-133), one launch
+ * behind wgcs_handshake_respond_batch: for descriptor j with d_gate[j] ==
+ * WGCS_HS_RESPONDED (respond's d_status) and d_resp[j].peer_row < n_peers,
+ * d_rekey[peer_row].last_sent_ns = now_ns.  n <= 2^28. */
+int wgcs_rekey_responded_batch(wgcs_ctx *ctx, const wgcs_hs_resp *d_resp, const int32_t *d_gate, uint32_t n,
+                               int64_t now_ns, wgcs_rekey *d_rekey, uint32_t n_peers, void *stream);
+
+/* SendHandshakeInitiation (send.go:84-100) up to CreateMessageInitiation, one
+ * lane per peer row, n_peers <= 2^24, n_tickets <= 2^28.  The tickets are
+ * n_tickets prefilled wgcs_hs_start rows (state_row, local_index, send_key,
+ * recv_key, timestamp, ephemeral_private; their peer_row, flags, cookie and
+ * pads are ignored), the arrangement of accept's tickets.  Peer row r, with
+ * w = want as it stood: d_reasons[r] = w, and d_status[r] =
+ *   w == 0                                              WGCS_HS_NONE
+ *   now_ns - last_sent_ns < WGCS_REKEY_TIMEOUT_NS       WGCS_ERR_REKEY_TIMEOUT; want = 0 (the reference
+ *                                                       drops the request, :89-98)
+ *   otherwise a candidate; candidates are ranked by row, ascending:
+ *     rank k < n_tickets                                WGCS_HS_STARTED: last_sent_ns = now_ns, want = 0,
+ *                                                       d_start_peer[k] = r, d_start[k] = ticket k with
+ *                                                       peer_row = r, flags = WGCS_HS_START_COOKIE and the
+ *                                                       cookie of d_hs_peers[r] where that row's
+ *                                                       WGCS_HS_PEER_COOKIE bit is set, else 0 and a zero
+ *                                                       cookie; pads 0
+ *     rank >= n_tickets                                 WGCS_ERR_BATCH_FULL; the row is untouched, so the
+ *                                                       wish survives to the next call
+ * *d_count = min(candidates, n_tickets).  The tail rows d_start[*d_count ..
+ * n_tickets) are all zero but for state_row = 0xFFFFFFFF, which
+ * wgcs_handshake_initiate_batch answers with WGCS_ERR_INVALID_ARG and nothing
+ * written; no ticket secret is copied into a tail row, and d_start_peer is
+ * WGCS_PEER_NONE there.  So initiate runs over n_tickets rows without reading
+ * the count.  n_peers == 0 sets *d_count = 0 and fills all n_tickets rows as
+ * the tail.  d_tickets and d_hs_peers are only read.  The call is accept's
+ * scheme of launches: verdict and candidates counted per block, a scan of the
+ * block counts, commit; which wave runs first does not change a byte of any
+ * output.  Its scratch is d_work, wgcs_keyorder_work_bytes(n_peers) bytes of
+ * the caller's device memory (WGCS_ERR_INVALID_ARG for fewer): nothing is
+ * allocated in an enqueue, and calls on other streams do not wait for it. */
+int wgcs_rekey_start_batch(wgcs_ctx *ctx, int64_t now_ns, wgcs_rekey *d_rekey, const wgcs_hs_peer *d_hs_peers,
+                           uint32_t n_peers, const wgcs_hs_start *d_tickets, uint32_t n_tickets,
+                           wgcs_hs_start *d_start, uint32_t *d_start_peer, uint32_t *d_count, int32_t *d_status,
+                           uint32_t *d_reasons, void *d_work, size_t work_bytes, void *stream);
+
+/* The six on host memory, no context and no device: the same row functions,
+ * taken in row order (the start form in the same passes), with the same tables
+ * and the same outputs.  WGCS_ERR_INVALID_ARG for a NULL pointer the device
+ * form refuses or a count over its bound; n == 0 a no-op. */
+int wgcs_rekey_recv_gate_host(wgcs_aead_pkt *pkts, uint32_t n, int64_t now_ns, const uint32_t *key_peer,
+                              uint32_t n_keys, const uint32_t *peer_rows, uint32_t n_ids, const wgcs_keypairs *kp,
+                              uint32_t n_peers);
+int wgcs_rekey_send_gate_host(const uint32_t *peer, const int32_t *count, const int32_t *status_in, uint32_t n_jobs,
+                              uint32_t max_segs, int64_t now_ns, const uint32_t *peer_rows, uint32_t n_ids,
+                              const wgcs_keypairs *kp, uint32_t n_peers, const uint64_t *send_nonce, uint32_t n_keys,
+                              uint64_t limit, wgcs_rekey *rekey, int32_t *status_out);
+int wgcs_rekey_sent_host(const uint32_t *peer, const int32_t *count, const int32_t *status, const uint32_t *job_key,
+                         uint32_t n_jobs, uint32_t max_segs, int64_t now_ns, const uint32_t *peer_rows, uint32_t n_ids,
+                         const wgcs_keypairs *kp, uint32_t n_peers, const uint64_t *send_nonce, uint32_t n_keys,
+                         uint64_t limit, wgcs_rekey *rekey);
+int wgcs_rekey_received_host(const wgcs_write_group *groups, uint32_t n_batches, uint32_t calls_per_batch,
+                             int64_t now_ns, const uint32_t *peer_rows, uint32_t n_ids, const wgcs_keypairs *kp,
+                             uint32_t n_peers, wgcs_rekey *rekey);
+int wgcs_rekey_responded_host(const wgcs_hs_resp *resp, const int32_t *gate, uint32_t n, int64_t now_ns,
+                              wgcs_rekey *rekey, uint32_t n_peers);
+int wgcs_rekey_start_host(int64_t now_ns, wgcs_rekey *rekey, const wgcs_hs_peer *hs_peers, uint32_t n_peers,
+                          const wgcs_hs_start *tickets, uint32_t n_tickets, wgcs_hs_start *start,
+                          uint32_t *start_peer, uint32_t *count, int32_t *status, uint32_t *reasons);
 
 #ifdef __cplusplus
 }

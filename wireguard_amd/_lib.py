@@ -41,6 +41,8 @@ ERR_LOW_ORDER = -22
 ERR_NO_PEER = -23
 ERR_NO_HANDSHAKE = -24
 ERR_FLOOD = -25
+ERR_KEY_EXPIRED = -26
+ERR_REKEY_TIMEOUT = -27
 ERR_HIP = -100
 ERR_NOMEM = -101
 ERR_NO_DEVICE = -102
@@ -64,6 +66,13 @@ HS_PEER_SEEN, HS_PEER_COOKIE = 0x1, 0x2  # wgcs_hs_peer.flags: the peer has cons
 HS_BEGUN = 8  # wgcs_keypairs_begin_*_batch's
 SESSION_NO_KEYPAIR = 0xFFFFFFFE  # a wgcs_session_slot key: the index is taken, its keypair is nil
 KEYPAIR_SET, KEYPAIR_INITIATOR = 0x1, 0x2  # wgcs_keypair_ref.flags
+HS_STARTED = 9  # wgcs_rekey_start_batch's
+SESSION_EXPIRED = 0xFFFFFFFD  # a wgcs_aead_pkt key: the keypair is past RejectAfterTime
+REJECT_AFTER_TIME_NS, REKEY_AFTER_TIME_NS = 180_000_000_000, 120_000_000_000  # constants.go:26, :15
+REKEY_TIMEOUT_NS, KEEPALIVE_TIMEOUT_NS = 5_000_000_000, 10_000_000_000  # :18, :30
+REKEY_LAST_MINUTE = 0x1  # wgcs_rekey.flags: timers.sentLastMinuteHandshake
+(REKEY_WANT_NO_KEYPAIR, REKEY_WANT_REJECT_MESSAGES, REKEY_WANT_REJECT_TIME, REKEY_WANT_REKEY_MESSAGES,
+ REKEY_WANT_REKEY_TIME, REKEY_WANT_LAST_MINUTE, REKEY_WANT_HOST) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40  # .want
 PEER_RUNNING = 0x1  # wgcs_peer_key.flags: peer.isRunning
 GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
 
@@ -243,6 +252,19 @@ def load() -> C.CDLL:
         "wgcs_keypairs_begin_initiator_host": ([vp, vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, u32, vp, vp, u32, vp,
                                                 u32, vp, vp, u32, vp], i32),
         "wgcs_keypairs_received_host": ([vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp], i32),
+        "wgcs_rekey_recv_gate_batch": ([vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, u32, vp], i32),
+        "wgcs_rekey_send_gate_batch": ([vp, vp, vp, vp, u32, u32, C.c_int64, vp, u32, vp, u32, vp, u32, u64, vp, vp, vp],
+                                       i32),
+        "wgcs_rekey_sent_batch": ([vp, vp, vp, vp, vp, u32, u32, C.c_int64, vp, u32, vp, u32, vp, u32, u64, vp, vp], i32),
+        "wgcs_rekey_received_batch": ([vp, vp, u32, u32, C.c_int64, vp, u32, vp, u32, vp, vp], i32),
+        "wgcs_rekey_responded_batch": ([vp, vp, vp, u32, C.c_int64, vp, u32, vp], i32),
+        "wgcs_rekey_start_batch": ([vp, C.c_int64, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, sz, vp], i32),
+        "wgcs_rekey_recv_gate_host": ([vp, u32, C.c_int64, vp, u32, vp, u32, vp, u32], i32),
+        "wgcs_rekey_send_gate_host": ([vp, vp, vp, u32, u32, C.c_int64, vp, u32, vp, u32, vp, u32, u64, vp, vp], i32),
+        "wgcs_rekey_sent_host": ([vp, vp, vp, vp, u32, u32, C.c_int64, vp, u32, vp, u32, vp, u32, u64, vp], i32),
+        "wgcs_rekey_received_host": ([vp, u32, u32, C.c_int64, vp, u32, vp, u32, vp], i32),
+        "wgcs_rekey_responded_host": ([vp, vp, u32, C.c_int64, vp, u32], i32),
+        "wgcs_rekey_start_host": ([C.c_int64, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

@@ -259,6 +259,8 @@ const char* wgcs_strerror(int status) {
     case WGCS_ERR_NO_PEER: return "no running peer with this public key";
     case WGCS_ERR_NO_HANDSHAKE: return "no handshake in flight under this receiver index";
     case WGCS_ERR_FLOOD: return "handshake flood";
+    case WGCS_ERR_KEY_EXPIRED: return "no current keypair, or it is past its message or time limit";
+    case WGCS_ERR_REKEY_TIMEOUT: return "within the rekey timeout of the last handshake sent";
     case WGCS_ERR_HIP: return "HIP runtime error";
     case WGCS_ERR_NOMEM: return "out of memory";
     case WGCS_ERR_NO_DEVICE: return "no HIP device";

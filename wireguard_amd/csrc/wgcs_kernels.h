@@ -152,4 +152,31 @@ hipError_t launch_keypairs_received(const wgcs_aead_pkt* pkts, const int32_t* ve
                                     wgcs_session_slot* peer_keys, uint32_t n_peer_slots, wgcs_aead_key* keys,
                                     uint32_t* rotated, hipStream_t s);
 
+// Keypair expiry, the rekey rules and the start of a handshake (rekey_kernels.hip, the row
+// functions of wgcs_rekey.h): one launch each, one lane per row, but launch_rekey_start, which
+// is accept's scheme over the peer rows -- verdict with the candidates of each 256-row block
+// counted, a one-block scan of those counts, commit with the tail descriptors -- or two launches
+// (scan, commit) when n_peers == 0.  block_cand is scratch of ceil(n_peers / 256) words.
+hipError_t launch_rekey_recv_gate(wgcs_aead_pkt* pkts, uint32_t n, int64_t now, const uint32_t* key_peer,
+                                  uint32_t n_keys, const uint32_t* peer_rows, uint32_t n_ids, const wgcs_keypairs* kp,
+                                  uint32_t n_peers, hipStream_t s);
+hipError_t launch_rekey_send_gate(const uint32_t* peer, const int32_t* count, const int32_t* status_in, uint32_t n_jobs,
+                                  uint32_t max_segs, int64_t now, const uint32_t* peer_rows, uint32_t n_ids,
+                                  const wgcs_keypairs* kp, uint32_t n_peers, const uint64_t* send_nonce,
+                                  uint32_t n_keys, uint64_t limit, wgcs_rekey* rekey, int32_t* status_out,
+                                  hipStream_t s);
+hipError_t launch_rekey_sent(const uint32_t* peer, const int32_t* count, const int32_t* status, const uint32_t* job_key,
+                             uint32_t n_jobs, uint32_t max_segs, int64_t now, const uint32_t* peer_rows,
+                             uint32_t n_ids, const wgcs_keypairs* kp, uint32_t n_peers, const uint64_t* send_nonce,
+                             uint32_t n_keys, uint64_t limit, wgcs_rekey* rekey, hipStream_t s);
+hipError_t launch_rekey_received(const wgcs_write_group* groups, uint32_t n, int64_t now, const uint32_t* peer_rows,
+                                 uint32_t n_ids, const wgcs_keypairs* kp, uint32_t n_peers, wgcs_rekey* rekey,
+                                 hipStream_t s);
+hipError_t launch_rekey_responded(const wgcs_hs_resp* resp, const int32_t* gate, uint32_t n, int64_t now,
+                                  wgcs_rekey* rekey, uint32_t n_peers, hipStream_t s);
+hipError_t launch_rekey_start(int64_t now, wgcs_rekey* rekey, const wgcs_hs_peer* hs_peers, uint32_t n_peers,
+                              const wgcs_hs_start* tickets, uint32_t n_tickets, wgcs_hs_start* start,
+                              uint32_t* start_peer, uint32_t* count, int32_t* status, uint32_t* reasons,
+                              uint32_t* block_cand, hipStream_t s);
+
 }  // namespace wgcs

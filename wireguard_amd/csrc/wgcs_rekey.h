@@ -1,0 +1,218 @@
+// wgcs_rekey.h -- keypair expiry, the rekey rules and the start of a handshake
+// as scalar row functions, shared by host and device:
+//   the receive gate           device/receive.go:162-170
+//   the send gate              device/send.go:368-374
+//   keepKeyFreshSending        send.go:213-227 (called at :523), with the goto top of :419-420
+//   keepKeyFreshReceiving      receive.go:80-91 (called at :486-488)
+//   SendHandshakeResponse      send.go:131-133, its lastSentHandshake alone
+//   SendHandshakeInitiation    send.go:84-100, up to CreateMessageInitiation
+// rekey_kernels.hip runs them one lane per row, rekey.cpp in row order, and the
+// stand-alone sanitizer program of tests/rekey_host/ includes this one text.
+//
+// The tables are those of include/wgcsum.h: one wgcs_rekey row beside every
+// wgcs_keypairs row, found from a peer id through wgcs_peer_rows_build's rows.
+// Every clock rule is now - x in signed 64 bits against a constant, so a clock
+// that went back fires no rule and, in the start call, counts as "within the
+// timeout".  Several rows of a call may belong to one peer: they only OR bits
+// into want and flags, so the tables come out the same whichever ran first.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/wgcsum.h"
+#include "wgcs_route_walk.h"
+
+namespace wgcs {
+
+constexpr uint32_t kRekeyNoKey = 0xFFFFFFFFu;  // send-assign's d_job_key of a dropped job
+
+static_assert(sizeof(wgcs_rekey) == 16 && sizeof(wgcs_hs_start) == 96 && sizeof(wgcs_hs_peer) == 64, "row layouts");
+
+// the row of the peer table that id names, or WGCS_PEER_NONE for "no row"
+WGCS_HD uint32_t rekey_peer_row(uint32_t id, const uint32_t* peer_rows, uint32_t n_ids, uint32_t n_peers) {
+  if (id >= n_ids) return WGCS_PEER_NONE;
+  const uint32_t row = peer_rows[id];
+  return row < n_peers ? row : WGCS_PEER_NONE;  // n_peers <= 2^24: WGCS_PEER_NONE itself is past it
+}
+
+WGCS_HD void rekey_want_or(wgcs_rekey* r, uint32_t bits) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicOr(&r->want, bits);
+#else
+  r->want |= bits;
+#endif
+}
+
+// ---- the receive gate, receive.go:162-170 ----
+
+WGCS_HD bool rekey_ref_receives(const wgcs_keypair_ref* r, uint32_t key) {
+  return (r->flags & WGCS_KEYPAIR_SET) && r->recv_key == key;
+}
+
+// true: row i's key is the receive key of one of its peer's three keypairs, and that keypair
+// is past RejectAfterTime (createdAt.Add(RejectAfterTime).Before(now): equality passes)
+WGCS_HD bool rekey_recv_expired(uint32_t i, const wgcs_aead_pkt* pkts, int64_t now, const uint32_t* key_peer,
+                                uint32_t n_keys, const uint32_t* peer_rows, uint32_t n_ids, const wgcs_keypairs* kp,
+                                uint32_t n_peers) {
+  const uint32_t key = pkts[i].key;
+  if (key >= n_keys) return false;
+  const uint32_t row = rekey_peer_row(key_peer[key], peer_rows, n_ids, n_peers);
+  if (row == WGCS_PEER_NONE) return false;
+  const wgcs_keypairs* const k = kp + row;
+  const wgcs_keypair_ref* ref = nullptr;  // sessions.Get(receiver).keypair
+  if (rekey_ref_receives(&k->current, key)) ref = &k->current;
+  else if (rekey_ref_receives(&k->previous, key)) ref = &k->previous;
+  else if (rekey_ref_receives(&k->next, key)) ref = &k->next;
+  return ref && now - ref->created_ns > WGCS_REJECT_AFTER_TIME_NS;
+}
+
+// ---- the send side: the gate in front of send-assign and keepKeyFreshSending behind it ----
+
+// The peer row of job j by send-assign's own rule (status 0, 1 <= count <= max_segs, the first
+// slot's peer), or WGCS_PEER_NONE for a job that is not taken or whose peer has no row.
+WGCS_HD uint32_t rekey_job_row(uint32_t j, const uint32_t* peer, const int32_t* count, const int32_t* status,
+                               uint32_t max_segs, const uint32_t* peer_rows, uint32_t n_ids, uint32_t n_peers) {
+  if (status[j] != 0) return WGCS_PEER_NONE;
+  const int32_t c = count[j];
+  if (c < 1 || (uint32_t)c > max_segs) return WGCS_PEER_NONE;
+  return rekey_peer_row(peer[(uint64_t)j * max_segs], peer_rows, n_ids, n_peers);
+}
+
+// send.go:368-374: what send-assign reads as job j's status
+WGCS_HD int32_t rekey_send_gate(uint32_t j, const uint32_t* peer, const int32_t* count, const int32_t* status_in,
+                                uint32_t max_segs, int64_t now, const uint32_t* peer_rows, uint32_t n_ids,
+                                const wgcs_keypairs* kp, uint32_t n_peers, const uint64_t* send_nonce, uint32_t n_keys,
+                                uint64_t limit, wgcs_rekey* rekey) {
+  const int32_t st = status_in[j];
+  const uint32_t row = rekey_job_row(j, peer, count, status_in, max_segs, peer_rows, n_ids, n_peers);
+  if (row == WGCS_PEER_NONE) return st;
+  const wgcs_keypair_ref* const cur = &kp[row].current;
+  uint32_t w = 0;
+  if (!(cur->flags & WGCS_KEYPAIR_SET)) {
+    w = WGCS_REKEY_WANT_NO_KEYPAIR;  // :369
+  } else {
+    const uint32_t key = cur->send_key;
+    if (key >= n_keys) return st;  // no nonce to read: send-assign's business
+    if (send_nonce[key] >= limit) w |= WGCS_REKEY_WANT_REJECT_MESSAGES;                      // :370
+    if (now - cur->created_ns >= WGCS_REJECT_AFTER_TIME_NS) w |= WGCS_REKEY_WANT_REJECT_TIME;  // :371
+  }
+  if (w == 0) return st;
+  rekey_want_or(rekey + row, w);  // :372
+  return WGCS_ERR_KEY_EXPIRED;    // :373: the job stays staged
+}
+
+// keepKeyFreshSending (send.go:213-227) for a kept job, the goto top of :419-420 for a dropped one
+WGCS_HD void rekey_sent(uint32_t j, const uint32_t* peer, const int32_t* count, const int32_t* status,
+                        const uint32_t* job_key, uint32_t max_segs, int64_t now, const uint32_t* peer_rows,
+                        uint32_t n_ids, const wgcs_keypairs* kp, uint32_t n_peers, const uint64_t* send_nonce,
+                        uint32_t n_keys, uint64_t limit, wgcs_rekey* rekey) {
+  const uint32_t row = rekey_job_row(j, peer, count, status, max_segs, peer_rows, n_ids, n_peers);
+  if (row == WGCS_PEER_NONE) return;
+  const wgcs_keypair_ref* const cur = &kp[row].current;
+  if (!(cur->flags & WGCS_KEYPAIR_SET)) return;  // :215-217
+  const bool has_nonce = cur->send_key < n_keys;
+  const uint64_t nonce = has_nonce ? send_nonce[cur->send_key] : 0;
+  uint32_t w = 0;
+  if (job_key[j] != kRekeyNoKey) {
+    if (nonce > WGCS_REKEY_AFTER_MESSAGES) w |= WGCS_REKEY_WANT_REKEY_MESSAGES;  // :223
+    if ((cur->flags & WGCS_KEYPAIR_INITIATOR) && now - cur->created_ns > WGCS_REKEY_AFTER_TIME_NS)
+      w |= WGCS_REKEY_WANT_REKEY_TIME;  // :224
+  } else if (has_nonce && nonce >= limit) {
+    w |= WGCS_REKEY_WANT_REJECT_MESSAGES;  // :385-390, :419-420 and then :370
+  }
+  if (w) rekey_want_or(rekey + row, w);
+}
+
+// ---- keepKeyFreshReceiving, receive.go:80-91, for one row of the write builder's groups ----
+
+WGCS_HD void rekey_received(uint32_t c, const wgcs_write_group* groups, int64_t now, const uint32_t* peer_rows,
+                            uint32_t n_ids, const wgcs_keypairs* kp, uint32_t n_peers, wgcs_rekey* rekey) {
+  if (groups[c].tail < 0) return;  // receive.go:486: no valid tail packet
+  const uint32_t row = rekey_peer_row(groups[c].peer, peer_rows, n_ids, n_peers);
+  if (row == WGCS_PEER_NONE) return;
+  const wgcs_keypair_ref* const cur = &kp[row].current;
+  const uint32_t both = WGCS_KEYPAIR_SET | WGCS_KEYPAIR_INITIATOR;
+  if ((cur->flags & both) != both) return;  // :85-86
+  if (!(now - cur->created_ns > WGCS_REJECT_AFTER_TIME_NS - WGCS_KEEPALIVE_TIMEOUT_NS - WGCS_REKEY_TIMEOUT_NS))
+    return;  // :87
+  wgcs_rekey* const r = rekey + row;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t old = atomicOr(&r->flags, WGCS_REKEY_LAST_MINUTE);  // :81, :88
+#else
+  const uint32_t old = r->flags;
+  r->flags = old | WGCS_REKEY_LAST_MINUTE;
+#endif
+  if (!(old & WGCS_REKEY_LAST_MINUTE)) rekey_want_or(r, WGCS_REKEY_WANT_LAST_MINUTE);  // :89
+}
+
+// ---- SendHandshakeResponse's lastSentHandshake, send.go:131-133 ----
+
+WGCS_HD void rekey_responded(uint32_t j, const wgcs_hs_resp* resp, const int32_t* gate, int64_t now, wgcs_rekey* rekey,
+                             uint32_t n_peers) {
+  if (gate[j] != WGCS_HS_RESPONDED) return;
+  const uint32_t row = resp[j].peer_row;
+  if (row < n_peers) rekey[row].last_sent_ns = now;
+}
+
+// ---- SendHandshakeInitiation, send.go:84-100, over the peer rows in three passes ----
+
+// The first pass, peer row r: WGCS_HS_NONE, WGCS_ERR_REKEY_TIMEOUT (the request is dropped, :89-98),
+// or WGCS_HS_STARTED for a candidate, which the last pass confirms or turns into WGCS_ERR_BATCH_FULL.
+WGCS_HD int rekey_start_verdict(uint32_t r, int64_t now, wgcs_rekey* rekey, uint32_t* reasons) {
+  wgcs_rekey* const k = rekey + r;
+  const uint32_t w = k->want;
+  reasons[r] = w;
+  if (w == 0) return WGCS_HS_NONE;
+  if (now - k->last_sent_ns < WGCS_REKEY_TIMEOUT_NS) {
+    k->want = 0;
+    return WGCS_ERR_REKEY_TIMEOUT;
+  }
+  return WGCS_HS_STARTED;
+}
+
+// The last pass, for the candidate r that rank candidates precede: its status.  A candidate with
+// a ticket takes it (:99) and writes its descriptor; one without leaves its row as it was.
+WGCS_HD int rekey_start_commit(uint32_t r, uint32_t rank, int64_t now, wgcs_rekey* rekey, const wgcs_hs_peer* hs_peers,
+                               const wgcs_hs_start* tickets, uint32_t n_tickets, wgcs_hs_start* start,
+                               uint32_t* start_peer) {
+  if (rank >= n_tickets) return WGCS_ERR_BATCH_FULL;
+  rekey[r].last_sent_ns = now;
+  rekey[r].want = 0;
+  start_peer[rank] = r;
+  const uint32_t* const t = (const uint32_t*)(tickets + rank);  // 96 B, 4-byte aligned
+  const uint32_t* const p = (const uint32_t*)(hs_peers + r);     // 64 B: flags at word 6, cookie at words 9..12
+  uint32_t* const d = (uint32_t*)(start + rank);
+  const bool cookie = (p[6] & WGCS_HS_PEER_COOKIE) != 0;
+  d[0] = t[0];  // state_row
+  d[1] = r;     // peer_row
+  d[2] = t[2];  // local_index
+  d[3] = t[3];  // send_key
+  d[4] = t[4];  // recv_key
+  d[5] = cookie ? WGCS_HS_START_COOKIE : 0u;
+  d[6] = t[6], d[7] = t[7], d[8] = t[8];  // timestamp
+  d[9] = 0;                               // pad0
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (uint32_t i = 10; i < 18; ++i) d[i] = t[i];  // ephemeral_private
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (uint32_t i = 0; i < 4; ++i) d[18 + i] = cookie ? p[9 + i] : 0u;
+  d[22] = d[23] = 0;  // pad1
+  return WGCS_HS_STARTED;
+}
+
+// descriptor k past the count: nothing for wgcs_handshake_initiate_batch to do, and no secret in it
+WGCS_HD void rekey_start_tail(uint32_t k, wgcs_hs_start* start, uint32_t* start_peer) {
+  uint32_t* const d = (uint32_t*)(start + k);
+  d[0] = 0xFFFFFFFFu;  // state_row past every table
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (uint32_t i = 1; i < sizeof(wgcs_hs_start) / 4; ++i) d[i] = 0;
+  start_peer[k] = WGCS_PEER_NONE;
+}
+
+}  // namespace wgcs
