@@ -53,6 +53,7 @@
  *                                                                  device/send.go:130-169
  *   wgcs_write_build_batch    one Tun.Write per receive batch and peer, with the peer's
  *                             bookkeeping (_host: on host arrays) device/receive.go:178-228, :398-504
+ *   wgcs_timers_*             the peer timers, their event hooks and their expiry  device/timers.go
  *   wgcs_stager_*             Tun.Read batch staging              tun/tun.go:477-508
  *   wgcs_wstager_*            Tun.Write batch staging             tun/tun.go:654-700
  * Status codes map 1:1 onto the reference's Go errors (see WGCS_ERR_*).
@@ -1426,10 +1427,11 @@ int wgcs_handshake_accept_host(const wgcs_hs_init *init, const int32_t *gate, ui
  * id into d_peer_keys, with the key WGCS_SESSION_NO_KEYPAIR.  That key is past
  * every key table (n_keys <= 2^24), so classify hands it on and open, replay,
  * send-assign and the write builder refuse it without touching a row.
- * The host keeps index allocation, the timers, SetEndpointFromPacket and
+ * The host keeps index allocation, SetEndpointFromPacket and
  * SendStagedPackets (from d_rotated), and the reclaiming of tombstoned slots
  * when it rebuilds a table.  Keypair expiry by created_ns is the next
- * section's (wgcs_rekey_recv_gate_batch, wgcs_rekey_send_gate_batch).
+ * section's (wgcs_rekey_recv_gate_batch, wgcs_rekey_send_gate_batch), the
+ * timers the one after it (wgcs_timers_rotated_batch reads d_rotated).
  *
  * DeleteSession(x) for a set entry x: the slot of x.local_index in d_slots
  * gets key WGCS_SESSION_NO_KEYPAIR, the 48-byte rows d_keys[x.send_key] and
@@ -1589,13 +1591,14 @@ int wgcs_keypairs_received_host(const wgcs_aead_pkt *pkts, const int32_t *verdic
  * value serves a whole call, where the reference reads the clock per packet.
  *
  * The host keeps: filling tickets (NewIndex, newPrivateKey, tai64n.Now);
- * sending the d_msgs rows that d_start_peer names; handshakeAttempts and the
- * retry timers (d_reasons tells a retry, WGCS_REKEY_WANT_HOST alone, from a
- * fresh request); timersHandshakeComplete, including clearing
- * WGCS_REKEY_LAST_MINUTE by a stream-ordered write when it handles a
- * WGCS_HS_BEGUN or d_rotated row -- until then the flag can only suppress a
- * request that a keypair seconds old could not raise; cookie ageing
- * (CookieRefreshTime) behind the WGCS_HS_PEER_COOKIE bit; expiredZeroOutKeys.
+ * sending the d_msgs rows that d_start_peer names; cookie ageing
+ * (CookieRefreshTime) behind the WGCS_HS_PEER_COOKIE bit.  handshakeAttempts,
+ * the retry timers, timersHandshakeComplete with the clearing of
+ * WGCS_REKEY_LAST_MINUTE, and expiredZeroOutKeys are the next section's
+ * (wgcs_timers_*): its expire call sets WGCS_REKEY_WANT_NEW_HANDSHAKE and
+ * WGCS_REKEY_WANT_RETRY, which d_reasons hands on.  A caller that keeps its
+ * timers on the host sets WGCS_REKEY_WANT_HOST and clears
+ * WGCS_REKEY_LAST_MINUTE by stream-ordered writes instead.
  *
  * The six calls share their conventions: asynchronous on stream (NULL: the
  * context's), ordinary launches in blocks of 256, no clock read, no randomness
@@ -1625,8 +1628,9 @@ int wgcs_keypairs_received_host(const wgcs_aead_pkt *pkts, const int32_t *verdic
 #define WGCS_REKEY_WANT_REKEY_MESSAGES 0x08u  /* :223 */
 #define WGCS_REKEY_WANT_REKEY_TIME 0x10u      /* :224 */
 #define WGCS_REKEY_WANT_LAST_MINUTE 0x20u     /* receive.go:85-89 */
-#define WGCS_REKEY_WANT_HOST 0x40u            /* the host's own timers (expiredNewHandshake, expiredResendHandshake),
-                                                 set by a stream-ordered write */
+#define WGCS_REKEY_WANT_HOST 0x40u            /* the timers of a caller that keeps them on the host (expiredNewHandshake,
+                                                 expiredResendHandshake), set by a stream-ordered write; the device's
+                                                 own are WGCS_REKEY_WANT_NEW_HANDSHAKE and WGCS_REKEY_WANT_RETRY below */
 
 typedef struct wgcs_rekey { /* 16 B, 8-byte aligned: row r belongs to d_table[r] */
   int64_t last_sent_ns;     /* handshake.lastSentHandshake on the caller's monotonic clock; the host
@@ -1759,6 +1763,261 @@ int wgcs_rekey_responded_host(const wgcs_hs_resp *resp, const int32_t *gate, uin
 int wgcs_rekey_start_host(int64_t now_ns, wgcs_rekey *rekey, const wgcs_hs_peer *hs_peers, uint32_t n_peers,
                           const wgcs_hs_start *tickets, uint32_t n_tickets, wgcs_hs_start *start,
                           uint32_t *start_peer, uint32_t *count, int32_t *status, uint32_t *reasons);
+
+/* ---- the peer timers: events, expiry, retry and keepalive
+ * (device/timers.go, with device/send.go:85-87, :117-126, :158-160, :193-209,
+ * :498-510, device/receive.go:311-312, :339-348, :422-427, :486-494 and
+ * device/peer.go:241-252) ----
+ * The five timers of a peer and the hooks that arm and cancel them, on the
+ * streams of the batches whose rows are the events: six event calls that sit
+ * behind the existing batches and read the rows those left in device memory,
+ * and one expire call over the peer rows that turns due timers into want bits
+ * (so wgcs_rekey_start_batch retries a lost handshake), into keepalive jobs in
+ * the layout wgcs_send_assign_batch takes, and into ZeroAndFlushAll's keypair
+ * part.  A lost initiation is noticed and retried on the device:
+ * initiate -> timers_initiated ... expire -> start -> initiate ->
+ * timers_initiated, with no read-back between them.
+ *
+ * The state is one wgcs_timers row beside every wgcs_keypairs and wgcs_rekey
+ * row; peers are found as in the section above.  A timer i is bit i of
+ * `pending` and deadline_ns[i]:
+ *   Mod(d)      sets the bit and stores deadline_ns[i] = now_ns + d
+ *   Del         clears the bit; deadline_ns[i] keeps the value it was last armed
+ *               with (0 in a fresh table), which nothing reads while the bit is clear
+ *   IsPending   reads the bit
+ * One now_ns serves a whole call; all clock arithmetic is signed 64-bit on the
+ * caller's clock (|values| < 2^62, keepalive_interval_s <= 65535 as the UAPI
+ * allows); a timer is due iff its bit is set and deadline_ns[i] <= now_ns, so a
+ * clock that went back fires nothing.  Every `if peer.timersActive()` of
+ * timers.go is a test of WGCS_TIMERS_ACTIVE, which only the host writes.
+ *
+ * No randomness is drawn: where timers.go adds rand.Int64N(
+ * RekeyTimeoutJitterMaxMs) milliseconds (:204, :271) the call takes a
+ * jitter_seed, and peer row r adds wgcs_timers_jitter_ms(jitter_seed, r) ms, in
+ * [0, 334): a fixed integer mix, so every row of one peer in one call computes
+ * the same deadline.
+ *
+ * Several rows of one call may belong to one peer.  A call only ORs bits into
+ * or ANDs bits out of the 32-bit words pending and flags (32-bit atomics), no
+ * call both sets and clears one bit, and every plain store of a call writes a
+ * value that is the same for all rows of the peer; `if !IsPending() { Mod }` is
+ * old = atomicOr, and only the lane that found the bit clear stores.  So the
+ * table afterwards is, byte for byte, what applying the rows one after the
+ * other in row order leaves, whichever wave ran first.
+ *
+ * The hooks, as the calls below name them (timers.go):
+ *   traversal        keepalive_interval_s > 0 and ACTIVE: keepalive.Mod(interval s)        :259-264
+ *   packet sent      ACTIVE: sendKeepalive.Del                                             :249-253
+ *   packet received  ACTIVE: newHandshake.Del                                              :226-230
+ *   data sent        ACTIVE and newHandshake not pending: Mod(15 s + jitter)               :189-221
+ *   data received    ACTIVE: sendKeepalive not pending: Mod(10 s), else NEED_ANOTHER       :235-244
+ *   initiated        ACTIVE: resendHandshake.Mod(5 s + jitter)                             :268-274
+ *   session derived  ACTIVE: zeroOutKeys.Mod(540 s)                                        :291-295
+ *   complete         ACTIVE: resendHandshake.Del; attempts = 0; WGCS_REKEY_LAST_MINUTE
+ *                    cleared in d_rekey; last_handshake_ns = now_ns                        :279-286
+ *
+ * The host keeps: index allocation and filling tickets; sending the messages
+ * and packets the calls prepared; the endpoint, which it clears when it reads
+ * and clears WGCS_TIMERS_CLEAR_SRC; the staged queue (FlushStagedPackets on
+ * WGCS_TIMERS_ACT_FLUSH_STAGED, d_staged); handshake.Clear and
+ * sessions.Delete(handshake.localIndex) after WGCS_TIMERS_ACT_ZEROED; cookie
+ * ageing and ConsumeReply; the rate limiter; WGCS_TIMERS_ACTIVE and
+ * keepalive_interval_s, by stream-ordered writes (timersStop clears pending).
+ *
+ * The seven calls share the conventions of the section above: asynchronous on
+ * stream (NULL: the context's), ordinary launches in blocks of 256, one lane
+ * per row, no clock read, aligned 4-byte or 8-byte accesses only, n == 0 a
+ * no-op.  WGCS_ERR_INVALID_ARG, nothing written, for a NULL pointer that is
+ * needed, a count over its bound or a misaligned pointer: d_timers, d_rekey,
+ * d_pkts and d_groups are 8-byte aligned, d_work 16-byte, everything else
+ * 4-byte.  n_peers <= 2^24. */
+
+#define WGCS_TIMER_NEW_HANDSHAKE 0    /* timers.newHandshake: expiredNewHandshake */
+#define WGCS_TIMER_RESEND_HANDSHAKE 1 /* timers.resendHandshake */
+#define WGCS_TIMER_SEND_KEEPALIVE 2   /* timers.sendKeepalive */
+#define WGCS_TIMER_KEEPALIVE 3        /* timers.keepalive: the persistent keepalive */
+#define WGCS_TIMER_ZERO_OUT_KEYS 4    /* timers.zeroOutKeys */
+#define WGCS_TIMERS_COUNT 5
+
+#define WGCS_TIMERS_ACTIVE 0x1u        /* wgcs_timers.flags: timersActive(); the host's to set */
+#define WGCS_TIMERS_NEED_ANOTHER 0x2u  /* timers.needAnotherKeepalive */
+#define WGCS_TIMERS_CLEAR_SRC 0x4u     /* markEndpointSrcForClearing: the endpoint is the host's, which reads and clears the bit */
+#define WGCS_TIMERS_KEEPALIVE_NOW 0x8u /* a SendKeepalive() is owed, receive.go:348; the expire call emits it */
+
+#define WGCS_TIMERS_JITTER_MAX_MS 334u     /* RekeyTimeoutJitterMaxMs, constants.go:24 */
+#define WGCS_TIMERS_MAX_ATTEMPTS 18u       /* MaxHandshakeAttempts, :19 */
+#define WGCS_TIMERS_ZERO_KEYS_NS 540000000000ll /* RejectAfterTime * 3, timers.go:100, :293 */
+
+#define WGCS_REKEY_WANT_NEW_HANDSHAKE 0x80u /* wgcs_rekey.want: expiredNewHandshake, SendHandshakeInitiation(false) */
+#define WGCS_REKEY_WANT_RETRY 0x100u        /* expiredResendHandshake, SendHandshakeInitiation(true) */
+
+/* d_actions of wgcs_timers_expire_batch: what happened in the row */
+#define WGCS_TIMERS_ACT_FIRED(i) (1u << (i)) /* bits 0..4: timer i's body ran */
+#define WGCS_TIMERS_ACT_KEEPALIVE 0x20u      /* a keepalive job was written for the peer */
+#define WGCS_TIMERS_ACT_DEFERRED 0x40u       /* a keepalive is owed, but n_ka_max jobs were taken: the next call emits it */
+#define WGCS_TIMERS_ACT_FLUSH_STAGED 0x80u   /* peer.FlushStagedPackets() is the host's to do */
+#define WGCS_TIMERS_ACT_ZEROED 0x100u        /* the three keypairs are deleted: handshake.Clear and its index are the host's */
+#define WGCS_TIMERS_ACT_GAVE_UP 0x200u       /* resendHandshake fired past MaxHandshakeAttempts, timers.go:85-101 */
+
+typedef struct wgcs_timers { /* 64 B, 8-byte aligned: row r belongs to d_table[r] */
+  int64_t deadline_ns[WGCS_TIMERS_COUNT]; /* when timer i fires, read only while bit i of pending is set */
+  int64_t last_handshake_ns;              /* peer.lastHandshake on the caller's clock; 0: never */
+  uint32_t pending;                       /* bit i: timers[i].isPending */
+  uint32_t attempts;                      /* timers.handshakeAttempts */
+  uint32_t flags;                         /* WGCS_TIMERS_* */
+  uint32_t keepalive_interval_s;          /* peer.keepaliveInterval */
+} wgcs_timers;
+
+/* The jitter of peer row `row` under `seed`, in [0, WGCS_TIMERS_JITTER_MAX_MS):
+ * x = seed ^ row * 0x9E3779B9; x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13;
+ * x *= 0xC2B2AE35; x ^= x >> 16 (all mod 2^32); the result is (x * 334) >> 32. */
+uint32_t wgcs_timers_jitter_ms(uint32_t seed, uint32_t row);
+
+/* send.go:498-510, one launch behind wgcs_send_assign_batch (and
+ * wgcs_rekey_sent_batch) over its inputs and d_job_key.  Job j counts iff it
+ * was kept (d_job_key[j] != 0xFFFFFFFF), d_status[j] == 0, 1 <= d_count[j] <=
+ * max_segs and its peer id d_peer[j * max_segs] has a row.  That row runs
+ * traversal and packet sent, and data sent too if some d_sizes[j * max_segs +
+ * k] != 0 for k < d_count[j] (a job of keepalives alone has only zero sizes).
+ * Only d_timers is written.  n_jobs * max_segs <= 2^28. */
+int wgcs_timers_sent_batch(wgcs_ctx *ctx, const int32_t *d_sizes, const uint32_t *d_peer, const int32_t *d_count,
+                           const int32_t *d_status, const uint32_t *d_job_key, uint32_t n_jobs, uint32_t max_segs,
+                           int64_t now_ns, uint32_t jitter_seed, const uint32_t *d_peer_rows, uint32_t n_ids,
+                           wgcs_timers *d_timers, uint32_t n_peers, void *stream);
+
+/* receive.go:486-494, one launch behind wgcs_write_build_batch over its
+ * n_batches * calls_per_batch rows of d_groups (<= 2^28).  A row with tail >=
+ * 0 whose peer has a row runs traversal and packet received; with
+ * WGCS_GROUP_DATA it runs data received: old = atomicOr(&pending,
+ * sendKeepalive), the lane that found the bit clear stores now_ns + 10 s, and
+ * every other lane sets WGCS_TIMERS_NEED_ANOTHER.  So two data groups of one
+ * peer in one call leave the timer armed and the flag set, as the reference's
+ * two turns do.  Only d_timers is written. */
+int wgcs_timers_received_batch(wgcs_ctx *ctx, const wgcs_write_group *d_groups, uint32_t n_batches,
+                               uint32_t calls_per_batch, int64_t now_ns, const uint32_t *d_peer_rows, uint32_t n_ids,
+                               wgcs_timers *d_timers, uint32_t n_peers, void *stream);
+
+/* send.go:85-87 and :117-126, behind wgcs_rekey_start_batch and
+ * wgcs_handshake_initiate_batch: two launches.  The first, over the n_peers
+ * rows: a row whose d_reasons[r] (start's) has any bit other than
+ * WGCS_REKEY_WANT_RETRY gets attempts = 0 (!isRetry), even when start answered
+ * WGCS_ERR_REKEY_TIMEOUT: :85-87 precede the timeout.  The second, over the
+ * n_tickets rows: ticket k with d_start_peer[k] < n_peers (start's; the tail
+ * rows hold WGCS_PEER_NONE) and d_init_status[k] == WGCS_HS_INITIATED
+ * (initiate's status) runs, on row d_start_peer[k], traversal, packet sent and
+ * initiated.  n_tickets <= 2^28 and may be 0; n_peers == 0 is a no-op.  Only
+ * d_timers is written. */
+int wgcs_timers_initiated_batch(wgcs_ctx *ctx, const uint32_t *d_reasons, const uint32_t *d_start_peer,
+                                const int32_t *d_init_status, uint32_t n_tickets, int64_t now_ns,
+                                uint32_t jitter_seed, wgcs_timers *d_timers, uint32_t n_peers, void *stream);
+
+/* One launch behind wgcs_handshake_respond_batch: descriptor j with d_gate[j]
+ * == WGCS_HS_RESPONDED (respond's d_status) and d_resp[j].peer_row < n_peers
+ * runs receive.go:311-312 (traversal, packet received) and then send.go:158-160
+ * (session derived, traversal, packet sent).  A descriptor that respond
+ * refused runs neither, where the reference had run :311-312 before it tried
+ * to respond.  n <= 2^28.  Only d_timers is written. */
+int wgcs_timers_responded_batch(wgcs_ctx *ctx, const wgcs_hs_resp *d_resp, const int32_t *d_gate, uint32_t n,
+                                int64_t now_ns, wgcs_timers *d_timers, uint32_t n_peers, void *stream);
+
+/* receive.go:339-348, one launch behind wgcs_keypairs_begin_initiator_batch
+ * over the same rows: row q counts iff d_begun[q] == WGCS_HS_BEGUN (begin's
+ * d_status); its peer row is found as begin found it (d_gate[q] ==
+ * WGCS_HS_FINISHED, LE32 msg[8:12] -> d_hs_slots -> d_states[row].peer_row),
+ * and a row for which that lookup fails or names a peer row >= n_peers is
+ * passed by.  The peer row runs traversal, packet received, session derived
+ * and complete, and gets WGCS_TIMERS_KEEPALIVE_NOW (:348).  d_timers and the
+ * flags of d_rekey are written.  n <= 2^24; n_hs_slots is 0 or a power of two. */
+int wgcs_timers_finished_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgcs_aead_pkt *d_pkts,
+                               const int32_t *d_gate, const int32_t *d_begun, uint32_t n, int64_t now_ns,
+                               const wgcs_session_slot *d_hs_slots, uint32_t n_hs_slots, const wgcs_hs_state *d_states,
+                               uint32_t n_states, wgcs_timers *d_timers, wgcs_rekey *d_rekey, uint32_t n_peers,
+                               void *stream);
+
+/* receive.go:422-427, one launch behind wgcs_keypairs_received_batch: row i
+ * with d_rotated[i] == 1, d_pkts[i].key < n_keys and a peer row for
+ * d_key_peer[key] runs complete on that row.  d_timers and the flags of
+ * d_rekey are written.  n <= 2^28. */
+int wgcs_timers_rotated_batch(wgcs_ctx *ctx, const wgcs_aead_pkt *d_pkts, const uint32_t *d_rotated, uint32_t n,
+                              int64_t now_ns, const uint32_t *d_key_peer, uint32_t n_keys, const uint32_t *d_peer_rows,
+                              uint32_t n_ids, wgcs_timers *d_timers, wgcs_rekey *d_rekey, uint32_t n_peers,
+                              void *stream);
+
+/* The timers' expiry over the peer rows, one lane per row, in the scheme of
+ * wgcs_rekey_start_batch: a verdict launch, a one-block scan of per-block
+ * counts, a commit launch; scratch is d_work, wgcs_keyorder_work_bytes(n_peers)
+ * bytes of the caller's device memory, and nothing is allocated.
+ *
+ * A row without WGCS_TIMERS_ACTIVE is left alone: d_actions[r] = 0.  An active
+ * row fires every timer that is due, in ascending order of deadline, ties by
+ * index; a timer's bit is cleared before its body runs (NewTimer's callback),
+ * and whatever a body arms is later than now_ns, so at most five bodies run:
+ *   newHandshake      flags |= CLEAR_SRC; want |= WGCS_REKEY_WANT_NEW_HANDSHAKE
+ *   resendHandshake   attempts > WGCS_TIMERS_MAX_ATTEMPTS: sendKeepalive.Del; actions GAVE_UP |
+ *                     FLUSH_STAGED; zeroOutKeys.Mod(540 s) if it is not pending
+ *                     otherwise: attempts += 1; flags |= CLEAR_SRC; want |= WGCS_REKEY_WANT_RETRY
+ *   sendKeepalive     a keepalive is owed; with NEED_ANOTHER: the flag is cleared and
+ *                     sendKeepalive.Mod(10 s)
+ *   keepalive         a keepalive is owed iff keepalive_interval_s > 0
+ *   zeroOutKeys       DeleteSession (the section above) of d_kp[r]'s current, previous and
+ *                     next, which become nil (peer.go:246-251), and the slot of
+ *                     d_table[r].peer in d_peer_keys gets WGCS_SESSION_NO_KEYPAIR; actions
+ *                     ZEROED | FLUSH_STAGED
+ * Each sets WGCS_TIMERS_ACT_FIRED(i).  WGCS_TIMERS_KEEPALIVE_NOW owes a
+ * keepalive too.  A row that owes one and has d_staged[r] != 0 (the host has
+ * staged packets for the peer, send.go:194; d_staged NULL: nobody has) emits
+ * none and its KEEPALIVE_NOW is cleared: SendStagedPackets is the caller's
+ * next send batch.  The other owing rows are ranked by row, ascending:
+ *   rank k < n_ka_max    job k in send-assign's layout with max_segs == 1: d_ka_peer[k] =
+ *                        d_table[r].peer, d_ka_count[k] = 1, d_ka_sizes[k] = 0, d_ka_status[k]
+ *                        = 0; KEEPALIVE_NOW is cleared; actions KEEPALIVE
+ *   rank >= n_ka_max     KEEPALIVE_NOW is set; actions DEFERRED
+ * *d_n_ka = min(owing rows, n_ka_max), and the tail rows [*d_n_ka, n_ka_max)
+ * are {WGCS_PEER_NONE, 0, 0, 0}, which wgcs_send_assign_batch drops by their
+ * count: the send chain runs over n_ka_max jobs without reading *d_n_ka.  One
+ * keepalive per peer and call, however many of its timers owe one.
+ * n_peers == 0 sets *d_n_ka = 0 and fills the n_ka_max rows as the tail.
+ * d_table and d_staged are only read; want bits are ORed into d_rekey.
+ * n_ka_max <= 2^24; n_slots and n_peer_slots are 0 or a power of two.  Two
+ * peers whose keypairs name one index or one key row are the caller's error. */
+int wgcs_timers_expire_batch(wgcs_ctx *ctx, int64_t now_ns, wgcs_timers *d_timers, wgcs_rekey *d_rekey,
+                             const wgcs_peer_key *d_table, uint32_t n_peers, const uint32_t *d_staged,
+                             wgcs_keypairs *d_kp, wgcs_session_slot *d_slots, uint32_t n_slots,
+                             wgcs_session_slot *d_peer_keys, uint32_t n_peer_slots, wgcs_aead_key *d_keys,
+                             uint32_t *d_key_peer, uint32_t n_keys, uint32_t n_ka_max, uint32_t *d_ka_peer,
+                             int32_t *d_ka_count, int32_t *d_ka_sizes, int32_t *d_ka_status, uint32_t *d_n_ka,
+                             uint32_t *d_actions, void *d_work, size_t work_bytes, void *stream);
+
+/* The seven on host memory, no context and no device: the same row functions,
+ * taken in row order (the expire form in the same passes), with the same tables
+ * and the same outputs.  WGCS_ERR_INVALID_ARG for a NULL pointer the device
+ * form refuses, a count over its bound or a slot count that is not 0 or a power
+ * of two; n == 0 a no-op. */
+int wgcs_timers_sent_host(const int32_t *sizes, const uint32_t *peer, const int32_t *count, const int32_t *status,
+                          const uint32_t *job_key, uint32_t n_jobs, uint32_t max_segs, int64_t now_ns,
+                          uint32_t jitter_seed, const uint32_t *peer_rows, uint32_t n_ids, wgcs_timers *timers,
+                          uint32_t n_peers);
+int wgcs_timers_received_host(const wgcs_write_group *groups, uint32_t n_batches, uint32_t calls_per_batch,
+                              int64_t now_ns, const uint32_t *peer_rows, uint32_t n_ids, wgcs_timers *timers,
+                              uint32_t n_peers);
+int wgcs_timers_initiated_host(const uint32_t *reasons, const uint32_t *start_peer, const int32_t *init_status,
+                               uint32_t n_tickets, int64_t now_ns, uint32_t jitter_seed, wgcs_timers *timers,
+                               uint32_t n_peers);
+int wgcs_timers_responded_host(const wgcs_hs_resp *resp, const int32_t *gate, uint32_t n, int64_t now_ns,
+                               wgcs_timers *timers, uint32_t n_peers);
+int wgcs_timers_finished_host(const uint8_t *arena, const wgcs_aead_pkt *pkts, const int32_t *gate,
+                              const int32_t *begun, uint32_t n, int64_t now_ns, const wgcs_session_slot *hs_slots,
+                              uint32_t n_hs_slots, const wgcs_hs_state *states, uint32_t n_states, wgcs_timers *timers,
+                              wgcs_rekey *rekey, uint32_t n_peers);
+int wgcs_timers_rotated_host(const wgcs_aead_pkt *pkts, const uint32_t *rotated, uint32_t n, int64_t now_ns,
+                             const uint32_t *key_peer, uint32_t n_keys, const uint32_t *peer_rows, uint32_t n_ids,
+                             wgcs_timers *timers, wgcs_rekey *rekey, uint32_t n_peers);
+int wgcs_timers_expire_host(int64_t now_ns, wgcs_timers *timers, wgcs_rekey *rekey, const wgcs_peer_key *table,
+                            uint32_t n_peers, const uint32_t *staged, wgcs_keypairs *kp, wgcs_session_slot *slots,
+                            uint32_t n_slots, wgcs_session_slot *peer_keys, uint32_t n_peer_slots,
+                            wgcs_aead_key *keys, uint32_t *key_peer, uint32_t n_keys, uint32_t n_ka_max,
+                            uint32_t *ka_peer, int32_t *ka_count, int32_t *ka_sizes, int32_t *ka_status,
+                            uint32_t *n_ka, uint32_t *actions);
 
 #ifdef __cplusplus
 }

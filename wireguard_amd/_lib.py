@@ -73,6 +73,14 @@ REKEY_TIMEOUT_NS, KEEPALIVE_TIMEOUT_NS = 5_000_000_000, 10_000_000_000  # :18, :
 REKEY_LAST_MINUTE = 0x1  # wgcs_rekey.flags: timers.sentLastMinuteHandshake
 (REKEY_WANT_NO_KEYPAIR, REKEY_WANT_REJECT_MESSAGES, REKEY_WANT_REJECT_TIME, REKEY_WANT_REKEY_MESSAGES,
  REKEY_WANT_REKEY_TIME, REKEY_WANT_LAST_MINUTE, REKEY_WANT_HOST) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40  # .want
+REKEY_WANT_NEW_HANDSHAKE, REKEY_WANT_RETRY = 0x80, 0x100  # .want: expiredNewHandshake, expiredResendHandshake
+(TIMER_NEW_HANDSHAKE, TIMER_RESEND_HANDSHAKE, TIMER_SEND_KEEPALIVE, TIMER_KEEPALIVE,
+ TIMER_ZERO_OUT_KEYS) = range(5)  # wgcs_timers: bit i of pending, deadline_ns[i]
+TIMERS_ACTIVE, TIMERS_NEED_ANOTHER, TIMERS_CLEAR_SRC, TIMERS_KEEPALIVE_NOW = 0x1, 0x2, 0x4, 0x8  # wgcs_timers.flags
+TIMERS_JITTER_MAX_MS, TIMERS_MAX_ATTEMPTS = 334, 18  # constants.go:24, :19
+TIMERS_ZERO_KEYS_NS = 3 * REJECT_AFTER_TIME_NS  # RejectAfterTime * 3
+(TIMERS_ACT_KEEPALIVE, TIMERS_ACT_DEFERRED, TIMERS_ACT_FLUSH_STAGED, TIMERS_ACT_ZEROED,
+ TIMERS_ACT_GAVE_UP) = 0x20, 0x40, 0x80, 0x100, 0x200  # wgcs_timers_expire_batch's d_actions; bits 0..4: timer i fired
 PEER_RUNNING = 0x1  # wgcs_peer_key.flags: peer.isRunning
 GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
 
@@ -265,6 +273,23 @@ def load() -> C.CDLL:
         "wgcs_rekey_received_host": ([vp, u32, u32, C.c_int64, vp, u32, vp, u32, vp], i32),
         "wgcs_rekey_responded_host": ([vp, vp, u32, C.c_int64, vp, u32], i32),
         "wgcs_rekey_start_host": ([C.c_int64, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp], i32),
+        "wgcs_timers_jitter_ms": ([u32, u32], u32),
+        "wgcs_timers_sent_batch": ([vp, vp, vp, vp, vp, vp, u32, u32, C.c_int64, u32, vp, u32, vp, u32, vp], i32),
+        "wgcs_timers_received_batch": ([vp, vp, u32, u32, C.c_int64, vp, u32, vp, u32, vp], i32),
+        "wgcs_timers_initiated_batch": ([vp, vp, vp, vp, u32, C.c_int64, u32, vp, u32, vp], i32),
+        "wgcs_timers_responded_batch": ([vp, vp, vp, u32, C.c_int64, vp, u32, vp], i32),
+        "wgcs_timers_finished_batch": ([vp, vp, vp, vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, vp, u32, vp], i32),
+        "wgcs_timers_rotated_batch": ([vp, vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, vp, u32, vp], i32),
+        "wgcs_timers_expire_batch": ([vp, C.c_int64, vp, vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, u32, u32, vp, vp,
+                                      vp, vp, vp, vp, vp, sz, vp], i32),
+        "wgcs_timers_sent_host": ([vp, vp, vp, vp, vp, u32, u32, C.c_int64, u32, vp, u32, vp, u32], i32),
+        "wgcs_timers_received_host": ([vp, u32, u32, C.c_int64, vp, u32, vp, u32], i32),
+        "wgcs_timers_initiated_host": ([vp, vp, vp, u32, C.c_int64, u32, vp, u32], i32),
+        "wgcs_timers_responded_host": ([vp, vp, u32, C.c_int64, vp, u32], i32),
+        "wgcs_timers_finished_host": ([vp, vp, vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, vp, u32], i32),
+        "wgcs_timers_rotated_host": ([vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, vp, u32], i32),
+        "wgcs_timers_expire_host": ([C.c_int64, vp, vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, u32, u32, vp, vp, vp,
+                                     vp, vp, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

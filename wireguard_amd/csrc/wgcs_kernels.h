@@ -179,4 +179,33 @@ hipError_t launch_rekey_start(int64_t now, wgcs_rekey* rekey, const wgcs_hs_peer
                               uint32_t* start_peer, uint32_t* count, int32_t* status, uint32_t* reasons,
                               uint32_t* block_cand, hipStream_t s);
 
+// The peer timers (timers_kernels.hip, the row functions of wgcs_timers.h): one launch each, one
+// lane per row, but launch_timers_initiated (the peer rows, then the tickets) and
+// launch_timers_expire, which is launch_rekey_start's scheme with the rows that owe a keepalive
+// job in the place of the candidates.  block_owe is scratch of ceil(n_peers / 256) words.
+hipError_t launch_timers_sent(const int32_t* sizes, const uint32_t* peer, const int32_t* count, const int32_t* status,
+                              const uint32_t* job_key, uint32_t n_jobs, uint32_t max_segs, int64_t now, uint32_t seed,
+                              const uint32_t* peer_rows, uint32_t n_ids, wgcs_timers* timers, uint32_t n_peers,
+                              hipStream_t s);
+hipError_t launch_timers_received(const wgcs_write_group* groups, uint32_t n, int64_t now, const uint32_t* peer_rows,
+                                  uint32_t n_ids, wgcs_timers* timers, uint32_t n_peers, hipStream_t s);
+hipError_t launch_timers_initiated(const uint32_t* reasons, const uint32_t* start_peer, const int32_t* init_status,
+                                   uint32_t n_tickets, int64_t now, uint32_t seed, wgcs_timers* timers,
+                                   uint32_t n_peers, hipStream_t s);
+hipError_t launch_timers_responded(const wgcs_hs_resp* resp, const int32_t* gate, uint32_t n, int64_t now,
+                                   wgcs_timers* timers, uint32_t n_peers, hipStream_t s);
+hipError_t launch_timers_finished(const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* gate,
+                                  const int32_t* begun, uint32_t n, int64_t now, const wgcs_session_slot* hs_slots,
+                                  uint32_t n_hs_slots, const wgcs_hs_state* states, uint32_t n_states,
+                                  wgcs_timers* timers, wgcs_rekey* rekey, uint32_t n_peers, hipStream_t s);
+hipError_t launch_timers_rotated(const wgcs_aead_pkt* pkts, const uint32_t* rotated, uint32_t n, int64_t now,
+                                 const uint32_t* key_peer, uint32_t n_keys, const uint32_t* peer_rows, uint32_t n_ids,
+                                 wgcs_timers* timers, wgcs_rekey* rekey, uint32_t n_peers, hipStream_t s);
+hipError_t launch_timers_expire(int64_t now, wgcs_timers* timers, wgcs_rekey* rekey, const wgcs_peer_key* table,
+                                uint32_t n_peers, const uint32_t* staged, wgcs_keypairs* kp, wgcs_session_slot* slots,
+                                uint32_t n_slots, wgcs_session_slot* peer_keys, uint32_t n_peer_slots,
+                                wgcs_aead_key* keys, uint32_t* key_peer, uint32_t n_keys, uint32_t n_ka_max,
+                                uint32_t* ka_peer, int32_t* ka_count, int32_t* ka_sizes, int32_t* ka_status,
+                                uint32_t* n_ka, uint32_t* actions, uint32_t* block_owe, hipStream_t s);
+
 }  // namespace wgcs
