@@ -120,7 +120,8 @@ def test_fewer_tickets_than_winners_in_a_wide_batch(dev):
 
 def test_more_blocks_than_one_turn_of_the_scan(dev):
     """1,024 * 256 + 300 rows: the scan kernel takes a second turn over the block counts, and a
-    winner's rank sums counts of both turns."""
+    winner's rank sums counts of both turns.  It is the one scan kernel (compact_kernels.hip) that
+    wgcs_rekey_start_batch and wgcs_timers_expire_batch launch too, so this covers their second turn."""
     n, n_peers = 1024 * 256 + 300, 3000
     rng = np.random.default_rng(262)
     table, rows, n_ids = cases.table_of(n_peers, seed=262)

@@ -228,6 +228,15 @@ def test_start_ranks_cross_block_edges(dev):
     assert not c["status"][:700].any() and c["count"][0] == 0 and not st.rekey["want"].any()
 
 
+def test_start_commit_grid_a_block_wider_than_the_verdict_grid(dev):
+    """300 peer rows, two verdict blocks, and 700 tickets, three commit blocks: the third fills tail descriptors only
+    and has no word among the block counts, which lie in a d_work of exactly keystate.work_bytes(300)"""
+    _, (o,) = twice(dev, cases.case("start_300_of_700", start_world(rows=(3, 299), n_peers=300), [cases.start_step(700, NOW)]))
+    assert o["count"][0] == 2 and o["start_peer"][:2].tolist() == [3, 299]
+    assert [int(o["status"][r]) for r in (3, 299, 100)] == [HS_STARTED, HS_STARTED, -27]
+    assert (o["start"]["state_row"][2:700] == 0xFFFFFFFF).all() and (o["start_peer"][2:700] == PEER_NONE).all()
+
+
 def test_start_without_peer_rows(dev):
     """n_peers == 0: the count is zero and every descriptor is the tail"""
     s = cases.start_step(5, NOW)

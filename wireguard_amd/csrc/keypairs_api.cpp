@@ -20,9 +20,6 @@ namespace {
 
 constexpr uint32_t kMaxReceived = 1u << 28;  // rows are counted in 32 bits
 
-inline bool pow2_or_zero(uint32_t x) { return (x & (x - 1)) == 0; }
-inline bool misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
-
 // what the two begin forms share: the tail of their argument lists
 int check_begin_tail(wgcs_ctx* ctx, const int32_t* d_gate, uint32_t n, const wgcs_peer_key* d_table, uint32_t n_peers,
                      const wgcs_keypairs* d_kp, const wgcs_session_slot* d_slots, uint32_t n_slots,
@@ -32,7 +29,7 @@ int check_begin_tail(wgcs_ctx* ctx, const int32_t* d_gate, uint32_t n, const wgc
       (n_peer_slots && !d_peer_keys))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
   if (d_gate == d_status) return set_err(ctx, WGCS_ERR_INVALID_ARG, "d_status must not be d_gate");
-  if (n > kKeyOrderMaxRows || n_peers > kKeyOrderMaxKeys || !pow2_or_zero(n_slots) || !pow2_or_zero(n_peer_slots))
+  if (n > kKeyOrderMaxRows || n_peers > kKeyOrderMaxKeys || !pow2_or_0(n_slots) || !pow2_or_0(n_peer_slots))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "n, n_peers <= 2^24, n_slots and n_peer_slots 0 or a power of two");
   if (misaligned(d_gate, 3) || misaligned(d_status, 3) || misaligned(d_table, 3) || misaligned(d_kp, 3) ||
       misaligned(d_slots, 3) || misaligned(d_peer_keys, 3) || misaligned(d_keys, 3) || misaligned(d_key_peer, 3) ||
@@ -95,7 +92,7 @@ int wgcs_keypairs_begin_initiator_batch(wgcs_ctx* ctx, const uint8_t* d_arena, c
   if (int rc = check_begin_tail(ctx, d_gate, n, d_table, n_peers, d_kp, d_slots, n_slots, d_peer_keys, n_peer_slots,
                                 d_keys, d_key_peer, d_status, d_work))
     return rc;
-  if (!pow2_or_zero(n_hs_slots) || misaligned(d_pkts, 7) || misaligned(d_hs_slots, 3) || misaligned(d_states, 3))
+  if (!pow2_or_0(n_hs_slots) || misaligned(d_pkts, 7) || misaligned(d_hs_slots, 3) || misaligned(d_states, 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG,
                    "n_hs_slots 0 or a power of two, 8-byte aligned d_pkts, 4-byte aligned d_hs_slots / d_states");
   std::lock_guard<std::mutex> g(ctx->mu);
@@ -120,7 +117,7 @@ int wgcs_keypairs_received_batch(wgcs_ctx* ctx, const wgcs_aead_pkt* d_pkts, con
   if (!d_pkts || !d_verdict || !d_rotated || (n_keys && (!d_key_peer || !d_keys)) || (n_ids && !d_peer_rows) ||
       (n_peers && !d_kp) || (n_slots && !d_slots) || (n_peer_slots && !d_peer_keys))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
-  if (n > kMaxReceived || !pow2_or_zero(n_slots) || !pow2_or_zero(n_peer_slots) || misaligned(d_pkts, 7) ||
+  if (n > kMaxReceived || !pow2_or_0(n_slots) || !pow2_or_0(n_peer_slots) || misaligned(d_pkts, 7) ||
       misaligned(d_verdict, 3) || misaligned(d_rotated, 3) || misaligned(d_key_peer, 3) || misaligned(d_keys, 3) ||
       misaligned(d_peer_rows, 3) || misaligned(d_kp, 3) || misaligned(d_slots, 3) || misaligned(d_peer_keys, 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG,

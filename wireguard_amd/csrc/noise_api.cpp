@@ -13,6 +13,7 @@
 #include <mutex>
 
 #include "../../include/wgcsum.h"
+#include "wgcs_compact.h"
 #include "wgcs_ctx.h"
 #include "wgcs_kernels.h"
 
@@ -152,7 +153,7 @@ int wgcs_handshake_accept_batch(wgcs_ctx* ctx, const wgcs_hs_init* d_init, const
   if (ctx->accept_pending && ctx->accept_stream != s &&
       (e = hipStreamWaitEvent(s, ctx->accept_ev, 0)) != hipSuccess)
     return hip_fail(ctx, e, "handshake_accept stream order");
-  const int rc = ensure_dev(ctx, ctx->d_accept, sizeof(uint32_t) * (size_t)(hs_accept_blocks(n) + 1));
+  const int rc = ensure_dev(ctx, ctx->d_accept, sizeof(uint32_t) * (size_t)(compact_blocks(n) + 1));
   if (rc != WGCS_OK) return rc;
   e = launch_hs_accept(d_init, d_gate, n, now_ns, d_table, d_peer_rows, n_ids, d_peers, n_peers, d_tickets, n_tickets,
                        d_resp, d_count, d_verdict, (uint32_t*)ctx->d_accept.ptr, s);

@@ -25,9 +25,6 @@ namespace {
 constexpr uint32_t kMaxRows = 1u << 28;   // rows are counted in 32 bits
 constexpr uint32_t kMaxPeers = 1u << 24;  // the expire call's lanes, and the bound of wgcs_keyorder_work_bytes
 
-inline bool misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
-inline bool pow2_or_0(uint32_t n) { return (n & (n - 1)) == 0; }
-
 // what the lookups of a lane need: id -> row -> timers
 int check_rows(wgcs_ctx* ctx, const uint32_t* d_peer_rows, uint32_t n_ids, const wgcs_timers* d_timers,
                uint32_t n_peers) {

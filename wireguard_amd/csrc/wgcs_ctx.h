@@ -22,6 +22,10 @@ struct HostBuf {
   size_t cap = 0;
 };
 
+// argument checks of the *_api.cpp files: p is not aligned to mask + 1 bytes; a table size the slot hash can mask
+inline bool misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
+inline bool pow2_or_0(uint32_t n) { return (n & (n - 1)) == 0; }
+
 int set_err(wgcs_ctx* ctx, int code, const char* fmt, ...);
 int hip_fail(wgcs_ctx* ctx, hipError_t e, const char* what);
 int ensure_dev(wgcs_ctx* ctx, DevBuf& b, size_t bytes);

@@ -120,11 +120,16 @@ hipError_t launch_hs_finish(const uint8_t* arena, const wgcs_aead_pkt* pkts, con
                             uint32_t n_peers, wgcs_aead_key* keys, uint32_t n_keys, uint8_t* work, int32_t* verdict,
                             hipStream_t s);
 
-// The responder's stateful tail (noise_accept_kernels.hip), one lane per row: four launches on
-// s -- claim, verdict with the winners of each 256-row block counted, a one-block scan of
-// those counts, commit with the tail descriptors -- or two (scan, commit) when n == 0.
-// block_winners is scratch of hs_accept_blocks(n) words, which the call owns until it is done.
-inline uint32_t hs_accept_blocks(uint32_t n) { return n / 256 + (n % 256 != 0); }
+// The scan of a call that compacts its flagged rows (wgcs_compact.h, compact_kernels.hip): one
+// block turns the n_blocks per-block counts into the counts below each block, and writes
+// *count = min(their sum, cap).  launch_hs_accept, launch_rekey_start and launch_timers_expire
+// each issue it between their verdict and commit launches, or in front of the commit alone when
+// they have no rows; their scratch is compact_blocks(rows) words of wgcs_compact.h.
+hipError_t launch_compact_scan(uint32_t* block_count, uint32_t n_blocks, uint32_t cap, uint32_t* count,
+                               hipStream_t s);
+
+// The responder's stateful tail (noise_accept_kernels.hip), one lane per row: claim, then the
+// scheme of wgcs_compact.h over the winners.  The call owns block_winners until it is done.
 hipError_t launch_hs_accept(const wgcs_hs_init* init, const int32_t* gate, uint32_t n, int64_t now,
                             const wgcs_peer_key* table, const uint32_t* peer_rows, uint32_t n_ids, wgcs_hs_peer* peers,
                             uint32_t n_peers, const wgcs_hs_ticket* tickets, uint32_t n_tickets, wgcs_hs_resp* resp,
@@ -154,9 +159,7 @@ hipError_t launch_keypairs_received(const wgcs_aead_pkt* pkts, const int32_t* ve
 
 // Keypair expiry, the rekey rules and the start of a handshake (rekey_kernels.hip, the row
 // functions of wgcs_rekey.h): one launch each, one lane per row, but launch_rekey_start, which
-// is accept's scheme over the peer rows -- verdict with the candidates of each 256-row block
-// counted, a one-block scan of those counts, commit with the tail descriptors -- or two launches
-// (scan, commit) when n_peers == 0.  block_cand is scratch of ceil(n_peers / 256) words.
+// is the scheme of wgcs_compact.h over the peer rows, the candidates flagged.
 hipError_t launch_rekey_recv_gate(wgcs_aead_pkt* pkts, uint32_t n, int64_t now, const uint32_t* key_peer,
                                   uint32_t n_keys, const uint32_t* peer_rows, uint32_t n_ids, const wgcs_keypairs* kp,
                                   uint32_t n_peers, hipStream_t s);
@@ -181,8 +184,8 @@ hipError_t launch_rekey_start(int64_t now, wgcs_rekey* rekey, const wgcs_hs_peer
 
 // The peer timers (timers_kernels.hip, the row functions of wgcs_timers.h): one launch each, one
 // lane per row, but launch_timers_initiated (the peer rows, then the tickets) and
-// launch_timers_expire, which is launch_rekey_start's scheme with the rows that owe a keepalive
-// job in the place of the candidates.  block_owe is scratch of ceil(n_peers / 256) words.
+// launch_timers_expire, which is the scheme of wgcs_compact.h over the peer rows, those that owe
+// a keepalive job flagged.
 hipError_t launch_timers_sent(const int32_t* sizes, const uint32_t* peer, const int32_t* count, const int32_t* status,
                               const uint32_t* job_key, uint32_t n_jobs, uint32_t max_segs, int64_t now, uint32_t seed,
                               const uint32_t* peer_rows, uint32_t n_ids, wgcs_timers* timers, uint32_t n_peers,

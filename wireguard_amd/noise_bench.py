@@ -363,7 +363,7 @@ def run_accept(args, dev, torch) -> None:
         res = {
             "metric": "handshake_accept_rows_per_s", "value": round(n / (accept_us * 1e-6)), "unit": "rows/s",
             "us_per_launch": round(accept_us, 2), "steps": args.steps, "warmup": args.warmup,
-            "kernel": "hs_accept_claim_kernel + hs_accept_verdict_kernel + hs_accept_scan_kernel + hs_accept_commit_kernel",
+            "kernel": "hs_accept_claim_kernel + hs_accept_verdict_kernel + compact_scan_kernel + hs_accept_commit_kernel",
             "timing": "HIP events around K calls; each call is a device copy that restores the peer rows, then the four launches",
             "peer_row_restore_us": round(restore_us, 2),
             "workload": {"rows": n, "peers": n_peers, "calling_peers": min(INITIATORS, n_peers), "tickets": nt,

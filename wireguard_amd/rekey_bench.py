@@ -153,7 +153,7 @@ def main() -> None:
                               "value": float(np.median([r[0] for r in rounds])), "us_per_call": [r[0] for r in rounds],
                               "table_restore_us_inside_each_call": [r[1] for r in rounds], "candidates": int(h_count[0]),
                               "tickets": P, "host_one_core_us": round(host_us, 2),
-                              "kernel": "rekey_start_verdict_kernel + rekey_start_scan_kernel + rekey_start_commit_kernel",
+                              "kernel": "rekey_start_verdict_kernel + compact_scan_kernel + rekey_start_commit_kernel",
                               "timing": "HIP events around K calls, three rounds alternating with the restore alone"}), flush=True)
         return
 

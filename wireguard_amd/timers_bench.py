@@ -185,7 +185,7 @@ def main() -> None:
                               "value": float(np.median([r[0] for r in rounds])), "us_per_call": [r[0] for r in rounds],
                               "table_restore_us_inside_each_call": [r[1] for r in rounds], "keepalive_jobs": int(o["n_ka"][0]),
                               "host_one_core_us": round(host_us, 2),
-                              "kernel": "timers_expire_verdict_kernel + timers_expire_scan_kernel + timers_expire_commit_kernel",
+                              "kernel": "timers_expire_verdict_kernel + compact_scan_kernel + timers_expire_commit_kernel",
                               "timing": "HIP events around K calls, three rounds alternating with the restore alone"}), flush=True)
         return
 
