@@ -44,6 +44,8 @@
  *   wgcs_cookie_*             CookieChecker / CookieGenerator      device/cookie.go
  *   wgcs_handshake_screen_batch  CheckMAC1, CheckMAC2 and the cookie reply at the top of
  *                             RoutineHandshake                     device/receive.go:270-287
+ *   wgcs_ratelimit_*          RateLimiter.Allow and cleanup between the screen and the Noise
+ *                             code of RoutineHandshake              ratelimiter/ratelimiter.go, device/receive.go:283-286
  *   wgcs_x25519 / _batch      curve25519.X25519                    device/noise_helpers.go:93-105
  *   wgcs_noise_* / wgcs_peer_keys_*  the stateless parts of the Noise handshake's two messages
  *                                                                  device/noise.go:344-457, :494-655
@@ -893,8 +895,9 @@ int wgcs_write_build_host(const wgcs_aead_pkt *pkts, const int32_t *verdict, uin
  * the old secret fails against the new one, and CreateReply would have
  * refreshed before sealing anyway.  The 24 random nonce bytes of every reply
  * (cookie.go:231) are the caller's as well; nothing here draws randomness or
- * reads a clock.  What comes after a pass -- the rate limiter, the Noise
- * handshake -- and IsUnderLoad's rule are the host's. */
+ * reads a clock.  What comes after a pass is the rate limiter (the
+ * wgcs_ratelimit_* section at the end of this header, on the device as well)
+ * and the Noise handshake; IsUnderLoad's rule is the host's. */
 typedef struct wgcs_cookie_checker { /* 96 B; 4-byte aligned on the device */
   uint8_t mac1_key[32];              /* BLAKE2s-256("mac1----" | pub)   cookie.go:106-109 */
   uint8_t cookie_key[32];            /* BLAKE2s-256("cookie--" | pub)   :112-114 */
@@ -1063,8 +1066,8 @@ int wgcs_x25519_batch(wgcs_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_
 /* ConsumeMessageInitiation up to :457 over the rows the screen passed: an
  * ordinary launch with the screen's contract (asynchronous on stream, n <=
  * 2^28, n == 0 a no-op, the arena only read, in the aligned 4-byte words that
- * hold a message).  d_gate is the screen's d_verdict -- the host's rate limiter
- * masks rows in it between the two launches when under load -- or NULL, which
+ * hold a message).  d_gate is the screen's d_verdict -- or, under load,
+ * wgcs_ratelimit_batch's, which masks rows in it between the two -- or NULL, which
  * selects every row of type 1; d_verdict must not be d_gate.  Row q:
  *   d_type[q] != 1 or d_gate[q] != WGCS_HS_PASS   d_verdict[q] = WGCS_HS_NONE; d_out[q] untouched,
  *                                                 nothing else read
@@ -1821,7 +1824,7 @@ int wgcs_rekey_start_host(int64_t now_ns, wgcs_rekey *rekey, const wgcs_hs_peer 
  * and clears WGCS_TIMERS_CLEAR_SRC; the staged queue (FlushStagedPackets on
  * WGCS_TIMERS_ACT_FLUSH_STAGED, d_staged); handshake.Clear and
  * sessions.Delete(handshake.localIndex) after WGCS_TIMERS_ACT_ZEROED; cookie
- * ageing and ConsumeReply; the rate limiter; WGCS_TIMERS_ACTIVE and
+ * ageing and ConsumeReply; the rate limiter's ticker; WGCS_TIMERS_ACTIVE and
  * keepalive_interval_s, by stream-ordered writes (timersStop clears pending).
  *
  * The seven calls share the conventions of the section above: asynchronous on
@@ -2018,6 +2021,116 @@ int wgcs_timers_expire_host(int64_t now_ns, wgcs_timers *timers, wgcs_rekey *rek
                             wgcs_aead_key *keys, uint32_t *key_peer, uint32_t n_keys, uint32_t n_ka_max,
                             uint32_t *ka_peer, int32_t *ka_count, int32_t *ka_sizes, int32_t *ka_status,
                             uint32_t *n_ka, uint32_t *actions);
+
+/* ---- the rate limiter between the screen and the Noise code
+ * (ratelimiter/ratelimiter.go, device/receive.go:283-286) ----
+ * Under load every initiation and response that passed MAC2 is charged to a
+ * token bucket of its source IP address: 20 packets a second sustained, a burst
+ * of 5.  MAC2 proves the source address; the bucket bounds what one proven
+ * address may cost the Noise code.  wgcs_ratelimit_batch sits between
+ * wgcs_handshake_screen_batch (under_load != 0) and
+ * wgcs_handshake_consume_batch on one stream, with nothing read back.
+ *
+ * The table is n_slots wgcs_rl_entry rows of the caller's memory, n_slots a
+ * power of two, 1 <= n_slots <= 2^24, all zero when new.  Open addressing:
+ * the entry of an address sits at its home slot
+ * wgcs_ratelimit_home_slot(src, n_slots) or at the first slot behind it, going
+ * round, that was empty when the address came.  Entries are never deleted in
+ * place, so a probe ends at the first empty slot; the cleanup call rebuilds the
+ * table without the idle entries instead.  The key of an address is (family,
+ * ip): a source of len 6 is family 4 with its 4 bytes then 12 zero bytes, len
+ * 18 family 16; the port is not part of it, and 1.2.3.4 and ::ffff:1.2.3.4 are
+ * two keys, as they are two netip.Addr values.
+ *
+ * One now_ns serves a whole call (|now_ns - last_ns| < 2^62; signed 64-bit
+ * arithmetic).  The m rows of one address in a call, in row order:
+ *   entry found   t0 = min(tokens + (now_ns - last_ns), WGCS_RL_MAX_TOKENS_NS);
+ *                 A = t0 >= WGCS_RL_PACKET_COST_NS ? t0 / WGCS_RL_PACKET_COST_NS : 0;
+ *                 the first min(m, A) rows pass, the others are refused;
+ *                 tokens = t0 - min(m, A) * WGCS_RL_PACKET_COST_NS, last_ns = now_ns
+ *                 (a refused call stores the capped tokens and the time too, :113-125)
+ *   not found     the first row makes the entry and passes (:96-108), and the
+ *                 first 1 + min(m - 1, 4) rows pass;
+ *                 tokens = (4 - min(m - 1, 4)) * WGCS_RL_PACKET_COST_NS, last_ns = now_ns
+ * which is what m calls of Allow leave when r.now() gives now_ns to each of
+ * them.  No address passes more than 5 rows in one call.
+ *
+ * Deviations from the reference: one clock value per call; the table is
+ * bounded, and an address that is new when no slot is free is refused with
+ * WGCS_ERR_RATE_TABLE_FULL (Go's map grows); netip.Addr's zone is not part of
+ * the key (DstToBytes carries none); rows of one address are charged in row
+ * order, where the reference's handshake workers leave the order open.
+ * IsUnderLoad and the cleanup ticker -- once a second while the last *d_live
+ * or entries_created was not zero -- stay with the host. */
+#define WGCS_ERR_RATE_LIMITED (-28)    /* rateLimiter.Allow said no: the message is dropped  receive.go:284-286 */
+#define WGCS_ERR_RATE_TABLE_FULL (-29) /* a new address and no free slot in the table: refused (the reference's map is unbounded) */
+
+#define WGCS_RL_PACKET_COST_NS 50000000ll /* packetCost, ratelimiter.go:14 */
+#define WGCS_RL_MAX_TOKENS_NS 250000000ll /* maxTokens = packetCost * packetsBurst, :19 */
+#define WGCS_RL_CLEANUP_NS 1000000000ll   /* cleanupInterval, :21 */
+#define WGCS_RL_CLAIMED 0x80000000u       /* wgcs_rl_entry.state inside a call: | the row that claimed the slot */
+
+typedef struct wgcs_rl_entry { /* 40 B, 8-byte aligned; all zero = empty */
+  uint8_t ip[16];              /* 4 address bytes then zeros, or 16 */
+  uint32_t state;              /* 0 empty, 1 live; inside a call also WGCS_RL_CLAIMED | row */
+  uint32_t family;             /* 4 or 16 */
+  int64_t tokens;              /* Entry.tokens, nanoseconds */
+  int64_t last_ns;             /* Entry.lastTime on the caller's clock */
+} wgcs_rl_entry;
+
+/* The home slot of src's address in a table of n_slots (a power of two; 0 for
+ * anything else, a NULL src or a len that is neither 6 nor 18): with w[0..3]
+ * the LE32 words of the 16 key bytes, h = 0x811C9DC5 ^ family; for each w[i]: h
+ * = (h ^ w[i]) * 0x01000193, h ^= h >> 15; then h ^= h >> 16, h *= 0x85EBCA6B,
+ * h ^= h >> 13, h *= 0xC2B2AE35, h ^= h >> 16 (all mod 2^32); h & (n_slots - 1). */
+uint32_t wgcs_ratelimit_home_slot(const wgcs_src_addr *src, uint32_t n_slots);
+
+/* One Allow on a table in host memory, no context and no device: 1 allowed, 0
+ * refused, WGCS_ERR_RATE_TABLE_FULL, or WGCS_ERR_INVALID_ARG for a NULL
+ * pointer, a bad n_slots or a len that is neither 6 nor 18. */
+int wgcs_ratelimit_allow(wgcs_rl_entry *table, uint32_t n_slots, const wgcs_src_addr *src, int64_t now_ns);
+
+/* The limiter over the rows of a receive batch.  Row q:
+ *   d_gate[q] != WGCS_HS_PASS                 d_verdict[q] = d_gate[q]; nothing else read
+ *   d_src[q].len neither 6 nor 18             WGCS_ERR_INVALID_ARG
+ *   a new address and no free slot            WGCS_ERR_RATE_TABLE_FULL, every row of it
+ *   otherwise                                 WGCS_HS_PASS or WGCS_ERR_RATE_LIMITED by the rule above
+ * Initiations and responses are both charged.  When more new addresses come
+ * than slots are free, which of them get the slots is unspecified here; the
+ * host form gives them out in row order.  d_verdict may be d_gate, and is what
+ * wgcs_handshake_consume_batch takes as its d_gate.  d_stats is optional: four
+ * words {passed, limited, table_full, entries_created}, written whole.
+ *
+ * Launches on stream (NULL: the context's), nothing allocated, no clock read:
+ * find-or-claim, one lane per row (an empty slot is claimed by a 32-bit
+ * compare-and-swap of state, and a claimed slot is compared with the claiming
+ * row's d_src, so no lane waits for another); the rows grouped by slot on the
+ * key order of wgcs_replay_batch; verdicts and entries, one lane per position,
+ * where the first row of a slot's run alone reads and writes the entry.  d_work
+ * is wgcs_keyorder_work_bytes(n) bytes of the caller's device memory, 16-byte
+ * aligned; d_table is 8-byte aligned, everything else 4-byte.  n <= 2^24; n ==
+ * 0 launches nothing but still writes d_stats.  WGCS_ERR_INVALID_ARG, nothing
+ * written, for a NULL pointer that is needed, a misaligned one, a bad n_slots,
+ * n over its bound or a workspace that is too small. */
+int wgcs_ratelimit_batch(wgcs_ctx *ctx, const int32_t *d_gate, const wgcs_src_addr *d_src, uint32_t n,
+                         wgcs_rl_entry *d_table, uint32_t n_slots, int64_t now_ns, int32_t *d_verdict,
+                         uint32_t *d_stats, void *d_work, size_t work_bytes, void *stream);
+
+/* cleanup() (:77-89) as a rebuild: d_new, which must not overlap d_old, is
+ * zeroed on the stream, and every live entry of d_old with now_ns - last_ns <=
+ * WGCS_RL_CLEANUP_NS is inserted into it; *d_live = the entries kept, 0 being
+ * the reference's "table is empty, stop the ticker".  The caller then uses
+ * d_new as the table.  One lane per slot of d_old; where an entry lands among
+ * the slots its probe may take depends on the order the lanes ran in. */
+int wgcs_ratelimit_cleanup_batch(wgcs_ctx *ctx, const wgcs_rl_entry *d_old, wgcs_rl_entry *d_new, uint32_t n_slots,
+                                 int64_t now_ns, uint32_t *d_live, void *stream);
+
+/* The two on host memory, no context and no device: the same row functions in
+ * the same passes, rows and slots taken in ascending order. */
+int wgcs_ratelimit_batch_host(const int32_t *gate, const wgcs_src_addr *src, uint32_t n, wgcs_rl_entry *table,
+                              uint32_t n_slots, int64_t now_ns, int32_t *verdict, uint32_t *stats);
+int wgcs_ratelimit_cleanup_host(const wgcs_rl_entry *old_table, wgcs_rl_entry *new_table, uint32_t n_slots,
+                                int64_t now_ns, uint32_t *live);
 
 #ifdef __cplusplus
 }

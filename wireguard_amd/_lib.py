@@ -43,6 +43,8 @@ ERR_NO_HANDSHAKE = -24
 ERR_FLOOD = -25
 ERR_KEY_EXPIRED = -26
 ERR_REKEY_TIMEOUT = -27
+ERR_RATE_LIMITED = -28
+ERR_RATE_TABLE_FULL = -29
 ERR_HIP = -100
 ERR_NOMEM = -101
 ERR_NO_DEVICE = -102
@@ -81,6 +83,8 @@ TIMERS_JITTER_MAX_MS, TIMERS_MAX_ATTEMPTS = 334, 18  # constants.go:24, :19
 TIMERS_ZERO_KEYS_NS = 3 * REJECT_AFTER_TIME_NS  # RejectAfterTime * 3
 (TIMERS_ACT_KEEPALIVE, TIMERS_ACT_DEFERRED, TIMERS_ACT_FLUSH_STAGED, TIMERS_ACT_ZEROED,
  TIMERS_ACT_GAVE_UP) = 0x20, 0x40, 0x80, 0x100, 0x200  # wgcs_timers_expire_batch's d_actions; bits 0..4: timer i fired
+RL_PACKET_COST_NS, RL_MAX_TOKENS_NS, RL_CLEANUP_NS = 50_000_000, 250_000_000, 1_000_000_000  # ratelimiter.go:14, :19, :21
+RL_CLAIMED = 0x80000000  # wgcs_rl_entry.state inside a call: | the claiming row
 PEER_RUNNING = 0x1  # wgcs_peer_key.flags: peer.isRunning
 GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
 
@@ -290,6 +294,12 @@ def load() -> C.CDLL:
         "wgcs_timers_rotated_host": ([vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, vp, u32], i32),
         "wgcs_timers_expire_host": ([C.c_int64, vp, vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, u32, u32, vp, vp, vp,
                                      vp, vp, vp], i32),
+        "wgcs_ratelimit_home_slot": ([vp, u32], u32),
+        "wgcs_ratelimit_allow": ([vp, u32, vp, C.c_int64], i32),
+        "wgcs_ratelimit_batch": ([vp, vp, vp, u32, vp, u32, C.c_int64, vp, vp, vp, sz, vp], i32),
+        "wgcs_ratelimit_cleanup_batch": ([vp, vp, vp, u32, C.c_int64, vp, vp], i32),
+        "wgcs_ratelimit_batch_host": ([vp, vp, u32, vp, u32, C.c_int64, vp, vp], i32),
+        "wgcs_ratelimit_cleanup_host": ([vp, vp, u32, C.c_int64, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

@@ -211,4 +211,14 @@ hipError_t launch_timers_expire(int64_t now, wgcs_timers* timers, wgcs_rekey* re
                                 uint32_t* ka_peer, int32_t* ka_count, int32_t* ka_sizes, int32_t* ka_status,
                                 uint32_t* n_ka, uint32_t* actions, uint32_t* block_owe, hipStream_t s);
 
+// The rate limiter (ratelimit_kernels.hip, the row functions of wgcs_ratelimit.h): find or claim,
+// one lane per row; the key order over the slots on a carved workspace (wgcs_keyorder.h); verdicts
+// and entries, one lane per position.  stats may be NULL; n == 0 only zeroes it.  The cleanup
+// zeroes new_table and *live on s, then one lane per old slot.
+hipError_t launch_ratelimit(const KeyOrder& ko, const int32_t* gate, const wgcs_src_addr* src, uint32_t n,
+                            wgcs_rl_entry* table, uint32_t n_slots, int64_t now, int32_t* verdict, uint32_t* stats,
+                            hipStream_t s);
+hipError_t launch_ratelimit_cleanup(const wgcs_rl_entry* old_table, wgcs_rl_entry* new_table, uint32_t n_slots,
+                                    int64_t now, uint32_t* live, hipStream_t s);
+
 }  // namespace wgcs
