@@ -947,8 +947,8 @@ int wgcs_cookie_consume_reply(const uint8_t cookie_key[32], const uint8_t last_m
  * through align_up(off + len, 4) (inside the contract of the other batch entry
  * points above).  Row q:
  *   d_type[q] other than 1 or 2   d_verdict[q] = WGCS_HS_NONE, nothing else read
- *                                 (transport rows, cookie replies -- ConsumeReply
- *                                 takes a per-peer lock and stays with the host --
+ *                                 (transport rows, cookie replies -- they are
+ *                                 wgcs_cookie_consume_batch's, last section --
  *                                 unknown and negative types)
  *   d_pkts[q].len != 148 (type 1) / 92 (type 2)   WGCS_ERR_INVALID_ARG, nothing read
  *   MAC1 of the message at d_pkts[q].off is wrong WGCS_ERR_MAC1
@@ -993,8 +993,9 @@ int wgcs_handshake_screen_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgc
  * runs here too, joined by a table of handshake states in device memory
  * (wgcs_handshake_initiate_batch and wgcs_handshake_finish_batch, the section
  * before the last).  Keypair rotation runs on the stream too (the wgcs_keypairs
- * calls of the last section).  What stays with the host is index allocation,
- * lastSentHandshake and the timers, and the consumption of cookie replies.
+ * calls of the last section).  What stays with the host is index allocation;
+ * lastSentHandshake, the timers and the consumption of cookie replies have
+ * sections of their own further down (wgcs_rekey_*, wgcs_timers_*, wgcs_cookie_*_batch).
  * Nothing here draws randomness or reads a clock. */
 
 /* curve25519.X25519 (RFC 7748 section 5; noise_helpers.go:93-105): the scalar is
@@ -1180,9 +1181,9 @@ int wgcs_handshake_respond_batch(wgcs_ctx *ctx, const wgcs_hs_resp *d_resp, uint
  * in flight, joins the two launches: wgcs_handshake_initiate_batch fills a row
  * and wgcs_handshake_finish_batch consumes it, so neither the ephemeral secret
  * nor a transport key of the initiator crosses to the host.  The host keeps
- * what the reference keeps under locks and clocks: sessions.NewIndex,
- * the timers, and the consumption of cookie replies
- * (wgcs_cookie_consume_reply); keypair rotation follows on the stream
+ * what the reference keeps under locks and clocks: sessions.NewIndex and
+ * the timers; cookie replies are consumed on the stream as well
+ * (wgcs_cookie_consume_batch, the last section); keypair rotation follows on the stream
  * (wgcs_keypairs_begin_initiator_batch), and lastSentHandshake with the
  * decision who needs a handshake is wgcs_rekey_start_batch's (the last
  * section), which writes d_start in device memory. */
@@ -1334,8 +1335,9 @@ typedef struct wgcs_hs_peer {    /* 64 B, 4-byte aligned: row r is the responder
   uint32_t flags;                /* WGCS_HS_PEER_SEEN | WGCS_HS_PEER_COOKIE */
   uint32_t remote_index;         /* hs.remoteIndex: the sender of the last initiation accepted */
   uint32_t claim;                /* 0xFFFFFFFF, or the lowest candidate row of the accept call in flight */
-  uint8_t cookie[16];            /* peer.cookieGenerator's cookie (cookie.go:287-314): the host writes it and
-                                    flags bit 1 when it consumes a cookie reply; the call only reads them */
+  uint8_t cookie[16];            /* peer.cookieGenerator's cookie (cookie.go:287-314): wgcs_cookie_consume_batch
+                                    writes it and flags bit 1, wgcs_cookie_age_batch clears the bit; the
+                                    accept and start calls only read them */
   uint8_t pad[12];               /* zero */
 } wgcs_hs_peer;
 #pragma pack(pop)
@@ -1594,8 +1596,9 @@ int wgcs_keypairs_received_host(const wgcs_aead_pkt *pkts, const int32_t *verdic
  * value serves a whole call, where the reference reads the clock per packet.
  *
  * The host keeps: filling tickets (NewIndex, newPrivateKey, tai64n.Now);
- * sending the d_msgs rows that d_start_peer names; cookie ageing
- * (CookieRefreshTime) behind the WGCS_HS_PEER_COOKIE bit.  handshakeAttempts,
+ * sending the d_msgs rows that d_start_peer names.  Cookie ageing
+ * (CookieRefreshTime) behind the WGCS_HS_PEER_COOKIE bit is wgcs_cookie_age_batch,
+ * which runs on the stream in front of this call (the last section).  handshakeAttempts,
  * the retry timers, timersHandshakeComplete with the clearing of
  * WGCS_REKEY_LAST_MINUTE, and expiredZeroOutKeys are the next section's
  * (wgcs_timers_*): its expire call sets WGCS_REKEY_WANT_NEW_HANDSHAKE and
@@ -1823,8 +1826,9 @@ int wgcs_rekey_start_host(int64_t now_ns, wgcs_rekey *rekey, const wgcs_hs_peer 
  * and packets the calls prepared; the endpoint, which it clears when it reads
  * and clears WGCS_TIMERS_CLEAR_SRC; the staged queue (FlushStagedPackets on
  * WGCS_TIMERS_ACT_FLUSH_STAGED, d_staged); handshake.Clear and
- * sessions.Delete(handshake.localIndex) after WGCS_TIMERS_ACT_ZEROED; cookie
- * ageing and ConsumeReply; the rate limiter's ticker; WGCS_TIMERS_ACTIVE and
+ * sessions.Delete(handshake.localIndex) after WGCS_TIMERS_ACT_ZEROED (cookie
+ * ageing and ConsumeReply are the wgcs_cookie_*_batch calls of the last
+ * section); the rate limiter's ticker; WGCS_TIMERS_ACTIVE and
  * keepalive_interval_s, by stream-ordered writes (timersStop clears pending).
  *
  * The seven calls share the conventions of the section above: asynchronous on
@@ -2131,6 +2135,149 @@ int wgcs_ratelimit_batch_host(const int32_t *gate, const wgcs_src_addr *src, uin
                               uint32_t n_slots, int64_t now_ns, int32_t *verdict, uint32_t *stats);
 int wgcs_ratelimit_cleanup_host(const wgcs_rl_entry *old_table, wgcs_rl_entry *new_table, uint32_t n_slots,
                                 int64_t now_ns, uint32_t *live);
+
+/* ---- the cookie generator: lastMAC1, ConsumeReply and ageing
+ * (device/cookie.go:247-339, device/receive.go:246-269) ----
+ * The initiator's side of the cookie mechanism.  A peer under load answers a
+ * handshake message without MAC2 by a cookie reply; the sender opens it with
+ * the MAC1 of the last message it sent that peer as additional data, keeps the
+ * cookie, and writes MAC2 with it for the next 120 s.  A table of
+ * wgcs_cookie_gen rows in device memory, row r belonging to d_table[r] and
+ * d_peers[r], holds what CookieGenerator holds beside the cookie itself.  The
+ * cookie and its valid bit stay where wgcs_handshake_accept_batch and
+ * wgcs_rekey_start_batch read them: wgcs_hs_peer.cookie and
+ * WGCS_HS_PEER_COOKIE.  With the four calls below the round trip runs on one
+ * stream with nothing read back:
+ *   initiate -> cookie_initiated ... the reply lands -> split -> classify ->
+ *   cookie_consume ... cookie_age -> timers expire / start -> initiate (MAC2)
+ * and on the responder's side respond -> cookie_responded.  Calls that touch
+ * one d_gen or d_peers table are ordered by the caller (one stream), as the
+ * calls of the sections above are.
+ *
+ * The clock is the caller's: one now_ns per call.  The host keeps
+ * peer.isRunning (receive.go:259; a reply for a stopped peer is the caller's
+ * to keep away), index allocation, and -- if it ever writes a cookie into
+ * d_peers itself -- cookie_set_at_ns: a host that writes wgcs_hs_peer.cookie
+ * and the bit also writes d_gen[r].cookie_set_at_ns, or does not call
+ * wgcs_cookie_age_batch. */
+#define WGCS_HS_COOKIE_KEPT 10          /* the cookie reply opened: its peer's row holds a cookie */
+#define WGCS_COOKIE_GEN_HAS_MAC1 0x1u   /* wgcs_cookie_gen.flags bit 0: hasLastMAC1 */
+#define WGCS_COOKIE_REFRESH_NS 120000000000ll /* CookieRefreshTime, cookie.go:17 */
+
+#pragma pack(push, 4)
+typedef struct wgcs_cookie_gen { /* 64 B, 4-byte aligned: row r is the generator of d_table[r] */
+  uint8_t cookie_key[32];        /* mac2.encryptionKey: BLAKE2s-256("cookie--" | remote static)  cookie.go:279-281 */
+  uint8_t last_mac1[16];         /* mac2.lastMAC1 */
+  int64_t cookie_set_at_ns;      /* mac2.cookieSetAt on the caller's monotonic clock */
+  uint32_t flags;                /* WGCS_COOKIE_GEN_HAS_MAC1 */
+  uint32_t claim;                /* 0 outside a call; inside one the highest row + 1 that wants the row */
+} wgcs_cookie_gen;
+#pragma pack(pop)
+
+/* CookieGenerator.Init (cookie.go:269-282) per peer row, host code: rows[r] =
+ * {cookie_key from table[r].public_key, everything else 0} for r < n.
+ * WGCS_ERR_INVALID_ARG for a NULL pointer with n != 0 or n > 2^24. */
+int wgcs_cookie_gen_build(const wgcs_peer_key *table, uint32_t n, wgcs_cookie_gen *rows);
+
+/* AddMACs' bookkeeping (cookie.go:301-302) behind wgcs_handshake_initiate_batch
+ * and behind wgcs_handshake_respond_batch, over the arrays those calls read and
+ * wrote.  Descriptor j takes part iff d_status[j] is WGCS_HS_INITIATED
+ * (WGCS_HS_RESPONDED for the responded form) and its peer_row < n_peers; its
+ * MAC1 is bytes [116, 132) of d_msgs + 160 * j (bytes [60, 76) of d_msgs + 96 *
+ * j).  The outcome is that of taking the descriptors in order: of several for
+ * one peer row the highest j leaves its MAC1 in last_mac1, and
+ * WGCS_COOKIE_GEN_HAS_MAC1 is set.  Rows no descriptor names change nothing,
+ * and nothing but last_mac1 and flags changes (claim is 0 again afterwards).
+ *
+ * Two launches, asynchronous on stream (NULL: the context's), one lane per
+ * descriptor: every one that takes part raises its row's claim to j + 1 (a
+ * 32-bit atomic max), then the holder alone stores the 16 bytes and the bit
+ * and puts claim back to 0, so no lane writes 16 bytes beside another lane
+ * writing the same 16 and the order of the waves does not show.  n <= 2^28, n
+ * == 0 or n_peers == 0 a no-op; everything is 4-byte aligned and read and
+ * written in 4-byte words.  WGCS_ERR_INVALID_ARG, nothing written, for a NULL
+ * pointer that is needed, a misaligned one, a count over its bound, or a d_gen
+ * that overlaps d_msgs. */
+int wgcs_cookie_initiated_batch(wgcs_ctx *ctx, const wgcs_hs_start *d_start, const int32_t *d_status,
+                                const uint8_t *d_msgs, uint32_t n, wgcs_cookie_gen *d_gen, uint32_t n_peers,
+                                void *stream);
+int wgcs_cookie_responded_batch(wgcs_ctx *ctx, const wgcs_hs_resp *d_resp, const int32_t *d_status,
+                                const uint8_t *d_msgs, uint32_t n, wgcs_cookie_gen *d_gen, uint32_t n_peers,
+                                void *stream);
+
+/* The cookie-reply case of RoutineHandshake (receive.go:246-269) with
+ * ConsumeReply (cookie.go:319-339) over the rows that wgcs_recv_classify_batch
+ * wrote, with the arena contract of wgcs_handshake_screen_batch: the arena is
+ * read and never written, messages sit at any byte offset and are read in the
+ * aligned 4-byte words that hold them.  Row q, in this order, with every table
+ * as it stood at launch:
+ *   d_type[q] != 3                                 d_verdict[q] = WGCS_HS_NONE, nothing else read
+ *   d_pkts[q].len != 64 or LE32 msg[0:4] != 3      WGCS_ERR_INVALID_ARG, no table read (unmarshal fails)
+ *   no peer row for receiver = LE32 msg[4:8]       WGCS_ERR_NO_PEER (session.peer == nil)
+ *   d_gen[row] lacks WGCS_COOKIE_GEN_HAS_MAC1      WGCS_ERR_NO_HANDSHAKE (!hasLastMAC1)
+ *   msg[32:64] does not open under cookie_key with nonce msg[8:32]
+ *   and last_mac1 as additional data               WGCS_ERR_AUTH
+ *   otherwise                                      WGCS_HS_COOKIE_KEPT
+ * The peer row of a receiver (d.indexTable.Lookup): (1) if receiver is in
+ * d_hs_slots with a row < n_states and d_states[row].local_index == receiver,
+ * in whatever state, it is that row's peer_row -- a handshake we initiated;
+ * (2) else, if receiver is in d_slots with a key < n_keys, d_key_peer[key] is
+ * an id < n_ids and d_peer_rows[id] < n_peers, it is d_peer_rows[id] -- a
+ * response we sent, which wgcs_keypairs_begin_responder_batch registered; (3)
+ * anything else is no peer: WGCS_SESSION_NO_KEYPAIR, an empty slot, a row at or
+ * past n_peers.
+ *
+ * Every row that opens for one peer gets WGCS_HS_COOKIE_KEPT, and the highest
+ * row's cookie is the one that stands (the reference, taking them in turn,
+ * overwrites): d_peers[row].cookie = that cookie, d_peers[row].flags |=
+ * WGCS_HS_PEER_COOKIE and no other bit, d_gen[row].cookie_set_at_ns = now_ns.
+ * last_mac1 and WGCS_COOKIE_GEN_HAS_MAC1 stay, as in the reference.  No other
+ * row of any table changes.
+ *
+ * Two launches on stream: the first opens every reply, leaves the cookie in
+ * d_work and claims the peer's row by an atomic max of q + 1; the second
+ * commits the holders, puts claim back to 0 and zeroes all of d_work, so no
+ * cookie outlives the call there.  d_work is 16 bytes of the caller's device
+ * memory per row.  No clock is read and no randomness drawn.  n <= 2^28, n ==
+ * 0 a no-op; slot counts are 0 or a power of two; d_pkts is 8-byte aligned,
+ * everything else 4-byte.  WGCS_ERR_INVALID_ARG, nothing written, for a NULL
+ * pointer that is needed, a misaligned one, a count over its bound, or when two
+ * of d_work, d_verdict, d_gen and d_peers overlap. */
+int wgcs_cookie_consume_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgcs_aead_pkt *d_pkts,
+                              const int32_t *d_type, uint32_t n, int64_t now_ns,
+                              const wgcs_session_slot *d_hs_slots, uint32_t n_hs_slots, const wgcs_hs_state *d_states,
+                              uint32_t n_states, const wgcs_session_slot *d_slots, uint32_t n_slots,
+                              const uint32_t *d_key_peer, uint32_t n_keys, const uint32_t *d_peer_rows, uint32_t n_ids,
+                              wgcs_cookie_gen *d_gen, wgcs_hs_peer *d_peers, uint32_t n_peers, void *d_work,
+                              int32_t *d_verdict, void *stream);
+
+/* The check AddMACs makes per message (cookie.go:306) with the clock standing
+ * at now_ns for the batch, one lane per peer row, on the stream in front of
+ * wgcs_handshake_accept_batch and wgcs_rekey_start_batch:
+ *   WGCS_HS_PEER_COOKIE set and now_ns - cookie_set_at_ns > WGCS_COOKIE_REFRESH_NS
+ *                      that bit of d_peers[r].flags is cleared and nothing else
+ *   any other row      untouched
+ * The difference is signed (|now_ns - cookie_set_at_ns| < 2^63): a clock that
+ * went back keeps the cookie, as time.Since would.  n_peers <= 2^24, 0 a no-op;
+ * WGCS_ERR_INVALID_ARG for a NULL or misaligned table or two that overlap. */
+int wgcs_cookie_age_batch(wgcs_ctx *ctx, int64_t now_ns, const wgcs_cookie_gen *d_gen, wgcs_hs_peer *d_peers,
+                          uint32_t n_peers, void *stream);
+
+/* The four on host memory, no context and no device: the same row functions
+ * in the same passes, rows taken in ascending order.  Tables, d_msgs and the
+ * work rows are 4-byte aligned; the arena is read by bytes and never outside a
+ * message. */
+int wgcs_cookie_initiated_host(const wgcs_hs_start *start, const int32_t *status, const uint8_t *msgs, uint32_t n,
+                               wgcs_cookie_gen *gen, uint32_t n_peers);
+int wgcs_cookie_responded_host(const wgcs_hs_resp *resp, const int32_t *status, const uint8_t *msgs, uint32_t n,
+                               wgcs_cookie_gen *gen, uint32_t n_peers);
+int wgcs_cookie_consume_host(const uint8_t *arena, const wgcs_aead_pkt *pkts, const int32_t *type, uint32_t n,
+                             int64_t now_ns, const wgcs_session_slot *hs_slots, uint32_t n_hs_slots,
+                             const wgcs_hs_state *states, uint32_t n_states, const wgcs_session_slot *slots,
+                             uint32_t n_slots, const uint32_t *key_peer, uint32_t n_keys, const uint32_t *peer_rows,
+                             uint32_t n_ids, wgcs_cookie_gen *gen, wgcs_hs_peer *peers, uint32_t n_peers, void *work,
+                             int32_t *verdict);
+int wgcs_cookie_age_host(int64_t now_ns, const wgcs_cookie_gen *gen, wgcs_hs_peer *peers, uint32_t n_peers);
 
 #ifdef __cplusplus
 }

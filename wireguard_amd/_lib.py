@@ -85,6 +85,9 @@ TIMERS_ZERO_KEYS_NS = 3 * REJECT_AFTER_TIME_NS  # RejectAfterTime * 3
  TIMERS_ACT_GAVE_UP) = 0x20, 0x40, 0x80, 0x100, 0x200  # wgcs_timers_expire_batch's d_actions; bits 0..4: timer i fired
 RL_PACKET_COST_NS, RL_MAX_TOKENS_NS, RL_CLEANUP_NS = 50_000_000, 250_000_000, 1_000_000_000  # ratelimiter.go:14, :19, :21
 RL_CLAIMED = 0x80000000  # wgcs_rl_entry.state inside a call: | the claiming row
+HS_COOKIE_KEPT = 10  # wgcs_cookie_consume_batch's
+COOKIE_GEN_HAS_MAC1 = 0x1  # wgcs_cookie_gen.flags: hasLastMAC1
+COOKIE_REFRESH_NS = 120_000_000_000  # CookieRefreshTime, cookie.go:17
 PEER_RUNNING = 0x1  # wgcs_peer_key.flags: peer.isRunning
 GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
 
@@ -300,6 +303,17 @@ def load() -> C.CDLL:
         "wgcs_ratelimit_cleanup_batch": ([vp, vp, vp, u32, C.c_int64, vp, vp], i32),
         "wgcs_ratelimit_batch_host": ([vp, vp, u32, vp, u32, C.c_int64, vp, vp], i32),
         "wgcs_ratelimit_cleanup_host": ([vp, vp, u32, C.c_int64, vp], i32),
+        "wgcs_cookie_gen_build": ([vp, u32, vp], i32),
+        "wgcs_cookie_initiated_batch": ([vp, vp, vp, vp, u32, vp, u32, vp], i32),
+        "wgcs_cookie_responded_batch": ([vp, vp, vp, vp, u32, vp, u32, vp], i32),
+        "wgcs_cookie_consume_batch": ([vp, vp, vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp,
+                                       u32, vp, vp, vp], i32),
+        "wgcs_cookie_age_batch": ([vp, C.c_int64, vp, vp, u32, vp], i32),
+        "wgcs_cookie_initiated_host": ([vp, vp, vp, u32, vp, u32], i32),
+        "wgcs_cookie_responded_host": ([vp, vp, vp, u32, vp, u32], i32),
+        "wgcs_cookie_consume_host": ([vp, vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp, u32,
+                                      vp, vp], i32),
+        "wgcs_cookie_age_host": ([C.c_int64, vp, vp, u32], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

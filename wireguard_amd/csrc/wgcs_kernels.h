@@ -221,4 +221,18 @@ hipError_t launch_ratelimit(const KeyOrder& ko, const int32_t* gate, const wgcs_
 hipError_t launch_ratelimit_cleanup(const wgcs_rl_entry* old_table, wgcs_rl_entry* new_table, uint32_t n_slots,
                                     int64_t now, uint32_t* live, hipStream_t s);
 
+// The cookie generator (cookiegen_kernels.hip, the row functions of wgcs_cookiegen.h), one lane
+// per row: initiated, responded and consume are a claim launch and a commit launch each, age one
+// launch over the peer rows.  The row count of a call is not 0.
+struct CookieGenTables;  // wgcs_cookiegen.h
+hipError_t launch_cookie_initiated(const wgcs_hs_start* start, const int32_t* status, const uint8_t* msgs, uint32_t n,
+                                   wgcs_cookie_gen* gen, uint32_t n_peers, hipStream_t s);
+hipError_t launch_cookie_responded(const wgcs_hs_resp* resp, const int32_t* status, const uint8_t* msgs, uint32_t n,
+                                   wgcs_cookie_gen* gen, uint32_t n_peers, hipStream_t s);
+hipError_t launch_cookie_consume(const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* types, uint32_t n,
+                                 int64_t now, const CookieGenTables& t, wgcs_cookie_gen* gen, wgcs_hs_peer* peers,
+                                 uint32_t* work, int32_t* verdict, hipStream_t s);
+hipError_t launch_cookie_age(int64_t now, const wgcs_cookie_gen* gen, wgcs_hs_peer* peers, uint32_t n_peers,
+                             hipStream_t s);
+
 }  // namespace wgcs
