@@ -56,7 +56,9 @@
  *   wgcs_write_build_batch    one Tun.Write per receive batch and peer, with the peer's
  *                             bookkeeping (_host: on host arrays) device/receive.go:178-228, :398-504
  *   wgcs_timers_*             the peer timers, their event hooks and their expiry  device/timers.go
- *   wgcs_stager_*             Tun.Read batch staging              tun/tun.go:477-508
+ *   wgcs_staged_*             peer.qus.staged: StagePackets, SendStagedPackets, FlushStagedPackets
+ *                                                                  device/send.go:331-426
+ *   wgcs_stager_*            Tun.Read batch staging              tun/tun.go:477-508
  *   wgcs_wstager_*            Tun.Write batch staging             tun/tun.go:654-700
  * Status codes map 1:1 onto the reference's Go errors (see WGCS_ERR_*).
  */
@@ -2278,6 +2280,137 @@ int wgcs_cookie_consume_host(const uint8_t *arena, const wgcs_aead_pkt *pkts, co
                              uint32_t n_ids, wgcs_cookie_gen *gen, wgcs_hs_peer *peers, uint32_t n_peers, void *work,
                              int32_t *verdict);
 int wgcs_cookie_age_host(int64_t now_ns, const wgcs_cookie_gen *gen, wgcs_hs_peer *peers, uint32_t n_peers);
+
+/* ---- the staged queue: peer.qus.staged on the device (device/send.go:331-426) ----
+ * The packets a peer cannot send yet -- no current keypair, or one past its
+ * limits -- wait in a ring per peer in the caller's device memory, beside the
+ * other per-peer tables: row r belongs to d_table[r], and a peer id finds its
+ * row through d_peer_rows / n_ids as in the rekey section.
+ *   uint32_t d_len[n_peers]              packets staged for the peer.  A plain word array: it is
+ *                                        what wgcs_timers_expire_batch takes as d_staged
+ *   uint32_t d_head[n_peers]             ring position of the oldest packet
+ *   uint32_t d_lost[n_peers]             packets evicted or flushed so far (PutQuOutItems), modulo 2^32
+ *   int32_t  d_slot_size[n_peers * cap]  the size of every slot's packet; 0 is a keepalive
+ *   uint8_t  d_ring[n_peers * cap * stride]  slot s = r * cap + pos holds its packet at s * stride + 16,
+ *                                        the send arena's layout with the header room in front
+ * cap is a power of two in [1, 1024], n_peers <= 2^24, n_peers * cap <= 2^28,
+ * stride a multiple of 16 (the arena's, the ring's and d_out's alike), d_ring,
+ * d_arena and d_out 16-byte aligned.  An all-zero state is the empty queue.
+ * The unit is the packet, not the reference's group of one Read's items, and
+ * eviction is oldest first per packet (the reference bounds a peer at
+ * QuStagedSize = 128 groups; cap = 128 is the recommended ring).
+ *
+ * All three calls are asynchronous on stream (NULL: the context's), ordinary
+ * launches, nothing allocated in an enqueue, no clock read.  Every ring slot
+ * and every output job has one writing lane group and the words of a peer one
+ * lane, so which wave runs first changes no byte of any output.
+ * WGCS_ERR_INVALID_ARG, nothing written, for a NULL pointer that is needed, a
+ * misaligned one, a cap that is no power of two, a count over its bound,
+ * d_ring overlapping d_arena or d_out, or scratch that is too small. */
+
+#define WGCS_STAGED_RELEASED 11        /* the peer's staged packets are jobs of the output table, its ring is empty */
+#define WGCS_STAGED_NONE 0xFFFFFFFFu    /* d_where: the slot is not staged */
+#define WGCS_STAGED_EVICTED 0xFFFFFFFEu /* d_where: staged and evicted within the call, never copied */
+
+/* StagePackets (send.go:331-350) and the re-staging of :402-407, behind
+ * wgcs_send_assign_batch over the job table the chain just ran on.  Job j is
+ * staged iff d_status_in[j] == 0, 1 <= d_count[j] <= max_segs, its peer
+ * d_peer[j * max_segs] has a row, and either the gate refused it
+ * (d_status_out[j] == WGCS_ERR_KEY_EXPIRED) or send-assign dropped it
+ * (d_status_out[j] == 0 and d_job_key[j] == 0xFFFFFFFF).  d_status_in and
+ * d_status_out are the gate's two arrays (two arrays: a gate that ran in
+ * place leaves no status_in to read).  A segment q = j * max_segs + k, k <
+ * d_count[j], is a packet of the job iff 0 <= d_sizes[q] and 16 + d_sizes[q] +
+ * 32 <= stride -- what wgcs_aead_seal_batch needs of a slot, stride being a
+ * multiple of 16; other segments are passed by.
+ *
+ * The packets of one peer in the call, in job order and then segment order,
+ * have ranks 0 .. m - 1.  With L = d_len[r] and head = d_head[r] before the
+ * call, rank k goes to ring position (head + L + k) & (cap - 1).  If L + m >
+ * cap the oldest L + m - cap packets are evicted, old ones first, then those of
+ * this call with k < m - cap, which are not copied at all: d_head advances and
+ * d_lost grows by that number, and d_len = min(L + m, cap).  Bytes [16, 16 +
+ * size) of the source slot are copied to the same range of the ring slot and
+ * d_slot_size[slot] = size; no other byte of d_ring or d_slot_size is written.
+ * d_where[q], for every q < n_jobs * max_segs, is the ring slot index,
+ * WGCS_STAGED_NONE or WGCS_STAGED_EVICTED.  The job table is only read.
+ *
+ * The jobs of one peer are ranked through the key order that replay,
+ * send-assign and the rate limiter use, the peer row as the key; d_work is
+ * wgcs_keyorder_work_bytes(n_jobs) bytes of scratch, 16-byte aligned.  The
+ * first launch counts the staged jobs into d_work; on a zero count -- most
+ * send batches -- the later launches return at once.  n_jobs <= 2^24,
+ * n_jobs * max_segs <= 2^28, n_jobs == 0 a no-op. */
+int wgcs_staged_stage_batch(wgcs_ctx *ctx, const uint8_t *d_arena, uint64_t stride, const int32_t *d_sizes,
+                            const uint32_t *d_peer, const int32_t *d_count, const int32_t *d_status_in,
+                            const int32_t *d_status_out, const uint32_t *d_job_key, uint32_t n_jobs, uint32_t max_segs,
+                            const uint32_t *d_peer_rows, uint32_t n_ids, uint32_t *d_len, uint32_t *d_head,
+                            uint32_t *d_lost, int32_t *d_slot_size, uint8_t *d_ring, uint32_t n_peers, uint32_t cap,
+                            uint32_t *d_where, void *d_work, size_t work_bytes, void *stream);
+
+/* SendStagedPackets (send.go:363-426) over the peer rows, wherever the
+ * reference calls it: at the head of a send batch, behind
+ * wgcs_keypairs_begin_initiator_batch and behind wgcs_keypairs_received_batch.
+ * Peer row r, d_status[r] =
+ *   d_len[r] == 0                            WGCS_HS_NONE
+ *   the send gate's rule fails (:368-374: current nil, d_send_nonce[current.send_key] >= limit,
+ *   now_ns - created_ns >= WGCS_REJECT_AFTER_TIME_NS)
+ *                                            WGCS_ERR_KEY_EXPIRED; the gate's want bits are OR-ed into
+ *                                            d_rekey[r].want, the ring is untouched
+ *   otherwise a candidate of weight d_len[r]; candidates are taken by row, ascending, P the weights
+ *   of the candidates below:
+ *     P + d_len[r] <= n_out_max              WGCS_STAGED_RELEASED: the packet at ring position
+ *                                            (head + i) & (cap - 1) becomes job k = P + i of the
+ *                                            output table, its bytes at [k * stride + 16, + size) of
+ *                                            d_out, d_out_peer[k] = d_table[r].peer, d_out_count[k] = 1,
+ *                                            d_out_sizes[k] = size, d_out_status[k] = 0; then
+ *                                            d_len[r] = d_head[r] = 0
+ *     otherwise                              WGCS_ERR_BATCH_FULL, the row untouched; P only grows, so
+ *                                            every candidate behind the first that does not fit is
+ *                                            deferred too
+ * *d_n_out = the jobs written, and rows [*d_n_out, n_out_max) of the output
+ * table are {WGCS_PEER_NONE, 0, 0, 0}, which send-assign drops by their count:
+ * the chain behind (send-assign with max_segs == 1, wgcs_rekey_sent_batch,
+ * wgcs_timers_sent_batch, seal, and wgcs_staged_stage_batch again for what
+ * send-assign dropped at the nonce limit) runs over n_out_max jobs without
+ * reading the count.  No byte of d_out outside a job's [16, 16 + size) is
+ * written.  The candidates are ranked by the count-scan-rank scheme of accept,
+ * start and expire with the packets of a row as its weight; d_work is
+ * wgcs_keyorder_work_bytes(n_peers) bytes of scratch.  n_out_max <= 2^28;
+ * n_peers == 0 sets *d_n_out = 0 and fills all n_out_max rows as the tail. */
+int wgcs_staged_release_batch(wgcs_ctx *ctx, int64_t now_ns, const wgcs_peer_key *d_table, const wgcs_keypairs *d_kp,
+                              const uint64_t *d_send_nonce, uint32_t n_keys, uint64_t limit, wgcs_rekey *d_rekey,
+                              uint32_t *d_len, uint32_t *d_head, const int32_t *d_slot_size, const uint8_t *d_ring,
+                              uint32_t n_peers, uint32_t cap, uint64_t stride, uint32_t n_out_max, uint8_t *d_out,
+                              uint32_t *d_out_peer, int32_t *d_out_count, int32_t *d_out_sizes, int32_t *d_out_status,
+                              uint32_t *d_n_out, int32_t *d_status, void *d_work, size_t work_bytes, void *stream);
+
+/* FlushStagedPackets (send.go:352-361), one lane per peer row over the
+ * d_actions of wgcs_timers_expire_batch: a row with
+ * WGCS_TIMERS_ACT_FLUSH_STAGED gets d_lost += d_len, d_len = 0, d_head = 0.
+ * d_actions == NULL flushes every row (peer.Stop, peer.go:259).  n_peers == 0
+ * a no-op. */
+int wgcs_staged_flush_batch(wgcs_ctx *ctx, const uint32_t *d_actions, uint32_t *d_len, uint32_t *d_head,
+                            uint32_t *d_lost, uint32_t n_peers, void *stream);
+
+/* The three on host memory, no context and no device: the same row functions,
+ * rows taken in row order, the same state and the same outputs.  The stage
+ * form's work is 16 * n_jobs bytes, 8-byte aligned (wgcs_keyorder_work_bytes
+ * (n_jobs) covers it); the release form needs none.  WGCS_ERR_INVALID_ARG, and
+ * nothing written, for what the device forms refuse. */
+int wgcs_staged_stage_host(const uint8_t *arena, uint64_t stride, const int32_t *sizes, const uint32_t *peer,
+                           const int32_t *count, const int32_t *status_in, const int32_t *status_out,
+                           const uint32_t *job_key, uint32_t n_jobs, uint32_t max_segs, const uint32_t *peer_rows,
+                           uint32_t n_ids, uint32_t *len, uint32_t *head, uint32_t *lost, int32_t *slot_size,
+                           uint8_t *ring, uint32_t n_peers, uint32_t cap, uint32_t *where, void *work,
+                           size_t work_bytes);
+int wgcs_staged_release_host(int64_t now_ns, const wgcs_peer_key *table, const wgcs_keypairs *kp,
+                             const uint64_t *send_nonce, uint32_t n_keys, uint64_t limit, wgcs_rekey *rekey,
+                             uint32_t *len, uint32_t *head, const int32_t *slot_size, const uint8_t *ring,
+                             uint32_t n_peers, uint32_t cap, uint64_t stride, uint32_t n_out_max, uint8_t *out,
+                             uint32_t *out_peer, int32_t *out_count, int32_t *out_sizes, int32_t *out_status,
+                             uint32_t *n_out, int32_t *status);
+int wgcs_staged_flush_host(const uint32_t *actions, uint32_t *len, uint32_t *head, uint32_t *lost, uint32_t n_peers);
 
 #ifdef __cplusplus
 }

@@ -90,6 +90,8 @@ COOKIE_GEN_HAS_MAC1 = 0x1  # wgcs_cookie_gen.flags: hasLastMAC1
 COOKIE_REFRESH_NS = 120_000_000_000  # CookieRefreshTime, cookie.go:17
 PEER_RUNNING = 0x1  # wgcs_peer_key.flags: peer.isRunning
 GROUP_DATA = 0x1  # wgcs_write_group.flags: dataPacketReceived, receive.go:436
+STAGED_RELEASED = 11  # wgcs_staged_release_batch's
+STAGED_NONE, STAGED_EVICTED = 0xFFFFFFFF, 0xFFFFFFFE  # wgcs_staged_stage_batch's d_where: not staged; evicted in the call
 
 
 class WgcsError(RuntimeError):
@@ -314,6 +316,16 @@ def load() -> C.CDLL:
         "wgcs_cookie_consume_host": ([vp, vp, vp, u32, C.c_int64, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, vp, u32,
                                       vp, vp], i32),
         "wgcs_cookie_age_host": ([C.c_int64, vp, vp, u32], i32),
+        "wgcs_staged_stage_batch": ([vp, vp, u64, vp, vp, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp, u32, u32,
+                                     vp, vp, sz, vp], i32),
+        "wgcs_staged_release_batch": ([vp, C.c_int64, vp, vp, vp, u32, u64, vp, vp, vp, vp, vp, u32, u32, u64, u32, vp, vp,
+                                       vp, vp, vp, vp, vp, vp, sz, vp], i32),
+        "wgcs_staged_flush_batch": ([vp, vp, vp, vp, vp, u32, vp], i32),
+        "wgcs_staged_stage_host": ([vp, u64, vp, vp, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp, u32, u32, vp,
+                                    vp, sz], i32),
+        "wgcs_staged_release_host": ([C.c_int64, vp, vp, vp, u32, u64, vp, vp, vp, vp, vp, u32, u32, u64, u32, vp, vp, vp,
+                                      vp, vp, vp, vp], i32),
+        "wgcs_staged_flush_host": ([vp, vp, vp, vp, u32], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

@@ -3,6 +3,8 @@
 // wgcs_handshake_accept_batch (winners into response descriptors), wgcs_rekey_start_batch
 // (candidates into start descriptors) and wgcs_timers_expire_batch (owing rows into keepalive
 // jobs) share it; their kernel files keep the row functions, the flag and the tail fill.
+// wgcs_staged_release_batch (ready peers into send jobs, a peer taking as many entries as it has
+// staged packets) uses the weighted form at the end of this file with the same scan kernel.
 //
 //   verdict kernel   one lane per row, kCompactThreads a block: judges its row, and
 //                    compact_count_block stores the flagged rows of the block in block_count[b]
@@ -69,6 +71,51 @@ __device__ inline uint32_t compact_rank(bool flag, const uint32_t* __restrict__ 
   if (flag) {
     rank = below[blockIdx.x] + (uint32_t)__popcll(ballot & ((1ull << lane) - 1));
     for (uint32_t w = 0; w < wave; ++w) rank += wave_flagged[w];
+  }
+  return rank;
+}
+
+// The weighted form (wgcs_staged_release_batch): a row takes w entries of the list, not one, so
+// the block word is the sum of the weights and a row's rank the weight of the rows below it.  The
+// scan is the same kernel -- it adds the block words whatever they count -- and *count comes out
+// as min(all weight, cap); a caller whose list ends at the first row that does not fit corrects
+// it in its commit kernel.  The sum of all weights stays below 2^32.
+
+// The tail of a weighted verdict kernel, every lane of the block: block_weight[blockIdx.x] = the
+// weights of its rows (0 for a row that is not flagged).
+__device__ inline void compact_weigh_block(uint32_t w, uint32_t* __restrict__ block_weight) {
+  __shared__ uint32_t wave_weight[kCompactThreads / kWave];
+  const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  uint32_t x = w;
+#pragma unroll
+  for (int d = kWave / 2; d > 0; d >>= 1) x += __shfl_down(x, d, kWave);
+  if (lane == 0) wave_weight[wave] = x;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t sum = 0;
+#pragma unroll
+    for (uint32_t v = 0; v < kCompactThreads / kWave; ++v) sum += wave_weight[v];
+    block_weight[blockIdx.x] = sum;
+  }
+}
+
+// The weight of the rows below a lane of a weighted commit kernel, every lane of the block; below
+// is block_weight behind the scan, read by the lanes with w != 0 only.
+__device__ inline uint32_t compact_weighted_rank(uint32_t w, const uint32_t* __restrict__ below) {
+  __shared__ uint32_t wave_weight[kCompactThreads / kWave];
+  const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  uint32_t x = w;  // the inclusive sum over the wave's lanes up to this one
+#pragma unroll
+  for (int d = 1; d < kWave; d <<= 1) {
+    const uint32_t y = __shfl_up(x, d, kWave);
+    if (lane >= (uint32_t)d) x += y;
+  }
+  if (lane == kWave - 1) wave_weight[wave] = x;
+  __syncthreads();
+  uint32_t rank = 0;
+  if (w) {
+    rank = below[blockIdx.x] + x - w;
+    for (uint32_t v = 0; v < wave; ++v) rank += wave_weight[v];
   }
   return rank;
 }

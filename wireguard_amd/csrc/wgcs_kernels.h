@@ -235,4 +235,29 @@ hipError_t launch_cookie_consume(const uint8_t* arena, const wgcs_aead_pkt* pkts
 hipError_t launch_cookie_age(int64_t now, const wgcs_cookie_gen* gen, wgcs_hs_peer* peers, uint32_t n_peers,
                              hipStream_t s);
 
+// The staged queue (staged_kernels.hip, the row functions of wgcs_staged.h).  Stage: the jobs'
+// rows as keys and a count of them, the key order over the peer rows on a carved workspace, one
+// wave per peer group for the ring words and the jobs' places, then 16 lanes per slot for the
+// copy; the launches behind the first exit on a zero count.  Release: the weighted form of
+// wgcs_compact.h over the peer rows (scratch: its block words, then one word per peer row), then
+// a block per released ring for the copy and the tail.  Flush: one lane per peer row.
+struct StagedRings {  // the state of include/wgcsum.h's staged section
+  uint32_t *len, *head, *lost;
+  int32_t* slot_size;
+  uint8_t* ring;
+  uint32_t n_peers, cap;
+  uint64_t stride;
+};
+hipError_t launch_staged_stage(const KeyOrder& ko, const uint8_t* arena, const int32_t* sizes, const uint32_t* peer,
+                               const int32_t* count, const int32_t* status_in, const int32_t* status_out,
+                               const uint32_t* job_key, uint32_t n_jobs, uint32_t max_segs, const uint32_t* peer_rows,
+                               uint32_t n_ids, const StagedRings& st, uint32_t* where, hipStream_t s);
+hipError_t launch_staged_release(int64_t now, const wgcs_peer_key* table, const wgcs_keypairs* kp,
+                                 const uint64_t* send_nonce, uint32_t n_keys, uint64_t limit, wgcs_rekey* rekey,
+                                 const StagedRings& st, uint32_t n_out_max, uint8_t* out, uint32_t* out_peer,
+                                 int32_t* out_count, int32_t* out_sizes, int32_t* out_status, uint32_t* n_out,
+                                 int32_t* status, uint32_t* work, hipStream_t s);
+hipError_t launch_staged_flush(const uint32_t* actions, uint32_t* len, uint32_t* head, uint32_t* lost, uint32_t n_peers,
+                               hipStream_t s);
+
 }  // namespace wgcs

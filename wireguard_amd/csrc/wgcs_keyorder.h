@@ -23,7 +23,8 @@ constexpr uint32_t kKeyOrderMaxRows = 1u << 24, kKeyOrderMaxKeys = 1u << 24;
 struct KeyOrder {
   uint32_t *keys_in, *slots_in;  // filled by the caller's own kernel (slots_in[i] = i)
   uint32_t *keys, *slots;        // sorted
-  uint32_t *heads, *n_heads;
+  uint32_t *heads, *n_heads;     // n_heads leads 256 bytes of its own: the words behind it are the caller's
+                                 // (stage: the count of staged jobs), and keyorder_sort zeroes *n_heads alone
   uint64_t* base;                // n words for the caller (send assign: a job's first nonce)
   void* sort_tmp;
   size_t sort_tmp_bytes;

@@ -79,6 +79,20 @@ WGCS_HD uint32_t rekey_job_row(uint32_t j, const uint32_t* peer, const int32_t* 
   return rekey_peer_row(peer[(uint64_t)j * max_segs], peer_rows, n_ids, n_peers);
 }
 
+// send.go:369-371 for peer row `row`: the reasons its current keypair cannot send, 0 for one that can.
+// The staged queue's release asks the same question per row (wgcs_staged.h).
+WGCS_HD uint32_t rekey_gate_want(uint32_t row, int64_t now, const wgcs_keypairs* kp, const uint64_t* send_nonce,
+                                 uint32_t n_keys, uint64_t limit) {
+  const wgcs_keypair_ref* const cur = &kp[row].current;
+  if (!(cur->flags & WGCS_KEYPAIR_SET)) return WGCS_REKEY_WANT_NO_KEYPAIR;  // :369
+  const uint32_t key = cur->send_key;
+  if (key >= n_keys) return 0;  // no nonce to read: send-assign's business
+  uint32_t w = 0;
+  if (send_nonce[key] >= limit) w |= WGCS_REKEY_WANT_REJECT_MESSAGES;                      // :370
+  if (now - cur->created_ns >= WGCS_REJECT_AFTER_TIME_NS) w |= WGCS_REKEY_WANT_REJECT_TIME;  // :371
+  return w;
+}
+
 // send.go:368-374: what send-assign reads as job j's status
 WGCS_HD int32_t rekey_send_gate(uint32_t j, const uint32_t* peer, const int32_t* count, const int32_t* status_in,
                                 uint32_t max_segs, int64_t now, const uint32_t* peer_rows, uint32_t n_ids,
@@ -87,16 +101,7 @@ WGCS_HD int32_t rekey_send_gate(uint32_t j, const uint32_t* peer, const int32_t*
   const int32_t st = status_in[j];
   const uint32_t row = rekey_job_row(j, peer, count, status_in, max_segs, peer_rows, n_ids, n_peers);
   if (row == WGCS_PEER_NONE) return st;
-  const wgcs_keypair_ref* const cur = &kp[row].current;
-  uint32_t w = 0;
-  if (!(cur->flags & WGCS_KEYPAIR_SET)) {
-    w = WGCS_REKEY_WANT_NO_KEYPAIR;  // :369
-  } else {
-    const uint32_t key = cur->send_key;
-    if (key >= n_keys) return st;  // no nonce to read: send-assign's business
-    if (send_nonce[key] >= limit) w |= WGCS_REKEY_WANT_REJECT_MESSAGES;                      // :370
-    if (now - cur->created_ns >= WGCS_REJECT_AFTER_TIME_NS) w |= WGCS_REKEY_WANT_REJECT_TIME;  // :371
-  }
+  const uint32_t w = rekey_gate_want(row, now, kp, send_nonce, n_keys, limit);
   if (w == 0) return st;
   rekey_want_or(rekey + row, w);  // :372
   return WGCS_ERR_KEY_EXPIRED;    // :373: the job stays staged
