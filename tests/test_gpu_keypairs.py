@@ -130,6 +130,25 @@ def test_begin_runs_of_one_peer_across_waves_and_blocks(dev):
     assert all(t[k].tobytes() == t2[k].tobytes() for k in TABLES)
 
 
+@pytest.mark.parametrize("place", ["highest_row_ends_at_n", "lowest_row_ends_at_a_key_change"])
+@pytest.mark.parametrize("k", [1, 2, 65])
+def test_begin_responder_run_lengths_and_ends(dev, k, place):
+    """k descriptors for one peer, which its lane takes in descriptor order: the peer's run of the key order ends
+    at n (the highest row, every descriptor taking part) or at the short run of another peer behind it."""
+    n, n_peers = k + 3, 5
+    rng = np.random.default_rng(650 + k)
+    idx = [int(x) for x in rng.choice(1 << 24, n, replace=False) + 1]
+    if place == "highest_row_ends_at_n":
+        row, peers = 4, [1] + [4] * k + [2, 1]
+    else:
+        row, peers = 0, [2] + [0] * k + [2, 2]
+    w = cases.world(n_peers, 2 * n + 2, idx, seed=651)
+    descs = [(p, idx[j], 2 * j, 2 * j + 1) for j, p in enumerate(peers)]
+    t, (status,) = check_case(dev, cases.case("run_of_%d" % k, w, [cases.resp_step(descs, seed=652)]))
+    assert status.tolist() == [HS_BEGUN] * n
+    assert int(t["kp"]["next"]["send_key"][row]) == 2 * k  # the run's last descriptor is the one that stays
+
+
 def wide_received(n=2 * 256 + 44, n_peers=12):
     """n rows; peer row 5's candidates at 3, 70 and 290, peer row 9's only in the last block (530 and 550), a
     third peer's candidate carries WGCS_ERR_REPLAY; the other rows run under current keys, keys of nobody and

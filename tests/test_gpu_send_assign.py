@@ -145,6 +145,23 @@ def test_many_jobs_of_one_key(dev):
     assert all(kept0[:90]) and not any(kept0[90:]) and after.tolist() == [limit, 50 + total[1], 0, 0]
 
 
+@pytest.mark.parametrize("place", ["highest_key_ends_at_n_jobs", "lowest_key_ends_at_a_key_change"])
+@pytest.mark.parametrize("k", [1, 63, 64, 65, 128, 129])
+def test_segment_lengths_around_the_trip(dev, k, place):
+    """One key with k jobs of one packet each, k around the 64 rows of a trip:
+    its segment ends at the end of the key order (the highest key row, every
+    job taking part) or at a short segment of another key behind it."""
+    first = [1000, 2000, 3000, 4000]
+    if place == "highest_key_ends_at_n_jobs":
+        walked, jobs = 3, [(1, 0, 100), (1, 0, 200)] + [(1, 0, 0)] * k  # peer id 0 has key row 3
+    else:
+        walked, jobs = 0, [(1, 0, 200)] + [(1, 0, 100)] * k + [(1, 0, 200), (1, 0, 200)]
+    nbufs, key, after = check(dev, jobs, first)
+    assert nbufs.tolist() == [1] * len(jobs)
+    assert (key == walked).sum() == k
+    assert int(after[walked]) == first[walked] + k
+
+
 def test_empty_batch_and_small_workspace(dev):
     L = dev.lib
     assert L.wgcs_send_assign_batch(dev.h, None, None, None, None, 0, MAX_SEGS, STRIDE, None, 1, None, 0, LIMIT, None,

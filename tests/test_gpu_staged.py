@@ -162,6 +162,26 @@ def test_more_than_a_block_and_a_trip(dev):
     assert o.status[266] == sc.STAGED_RELEASED and not d.st.len.any()
 
 
+@pytest.mark.parametrize("place", ["highest_row_ends_at_n_jobs", "lowest_row_ends_at_a_key_change"])
+@pytest.mark.parametrize("k", [1, 63, 64, 65, 128, 129])
+def test_segment_lengths_around_the_trip(dev, k, place):
+    """k jobs of one packet each for one peer, k around the 64 jobs of a trip, into a ring of 128: the peer's segment
+    ends at the end of the key order (the highest row, every job staged) or at a short segment of another peer behind
+    it; 129 jobs also cross the eviction edge inside the third trip's first row"""
+    rng = np.random.default_rng(1000 + k)
+    w = sc.world(rng, 3, 128, stride=64)
+    d = DeviceDriver(dev, w)
+    ids = [int(x) for x in w.ids]
+    one = lambda r, i: (ids[r], [i % 17], 0)  # a slot of 64 bytes holds 16 of a packet
+    if place == "highest_row_ends_at_n_jobs":
+        row, spec = 2, [one(0, 3), one(1, 5)] + [one(2, i) for i in range(k)]
+    else:
+        row, spec = 0, [one(1, 3)] + [one(0, i) for i in range(k)] + [one(1, 5), one(1, 7)]
+    where = d.stage(sc.refused(rng, w, spec))
+    assert (where == sc.STAGED_NONE).sum() == 0 and (where == sc.STAGED_EVICTED).sum() == max(k - 128, 0)
+    assert d.st.len[row] == min(k, 128) and d.st.lost[row] == max(k - 128, 0)
+
+
 def test_what_is_refused_writes_nothing(dev):
     rng = np.random.default_rng(2)
     w = sc.world(rng, 3, 4)

@@ -21,15 +21,13 @@ static_assert(sizeof(wgcs_aead_key) == 48 && sizeof(wgcs_aead_pkt) == 24, "wgcsu
 
 namespace {
 
-constexpr uint32_t kMaxBatch = 1u << 28;  // rows are counted in 32 bits
-
 int batch(wgcs_ctx* ctx, int open, uint8_t* d_arena, const wgcs_aead_pkt* d_pkts, const wgcs_aead_key* d_keys,
           uint32_t n_keys, uint32_t n, uint32_t mtu, int32_t* d_len, uint64_t* d_counter, void* stream) {
   if (!ctx) return WGCS_ERR_INVALID_ARG;
   if (n == 0) return WGCS_OK;
   if (!d_arena || !d_pkts || !d_len || (open && !d_counter) || (n_keys && !d_keys))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
-  if (n > kMaxBatch || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_keys & 3) || ((uintptr_t)d_len & 3) ||
+  if (n > kMaxRows || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_keys & 3) || ((uintptr_t)d_len & 3) ||
       ((uintptr_t)d_counter & 7))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "n <= 2^28, 8-byte aligned d_pkts / d_counter, 4-byte aligned d_keys");
   std::lock_guard<std::mutex> g(ctx->mu);

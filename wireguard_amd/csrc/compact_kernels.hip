@@ -20,12 +20,7 @@ __global__ __launch_bounds__(kScanThreads) void compact_scan_kernel(uint32_t* __
   for (uint32_t first = 0; first < n_blocks; first += kScanThreads) {
     const uint32_t b = first + threadIdx.x;
     const uint32_t mine = b < n_blocks ? block_count[b] : 0;
-    uint32_t x = mine;  // the inclusive sum over the wave's lanes up to this one
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const uint32_t y = __shfl_up(x, d, kWave);
-      if (lane >= (uint32_t)d) x += y;
-    }
+    const uint32_t x = wave_scan(mine, lane, WaveSum());
     if (lane == kWave - 1) wave_sum[wave] = x;
     __syncthreads();
     uint32_t waves_below = 0, turn = 0;

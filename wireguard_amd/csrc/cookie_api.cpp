@@ -13,12 +13,6 @@
 
 using namespace wgcs;
 
-namespace {
-
-constexpr uint32_t kMaxBatch = 1u << 28;  // rows are counted in 32 bits
-
-}  // namespace
-
 extern "C" {
 
 int wgcs_handshake_screen_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const wgcs_aead_pkt* d_pkts,
@@ -29,7 +23,7 @@ int wgcs_handshake_screen_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const wgc
   if (n == 0) return WGCS_OK;
   if (!d_arena || !d_pkts || !d_type || !d_checker || !d_verdict || (under_load && (!d_src || !d_nonce || !d_reply)))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
-  if (n > kMaxBatch || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_type & 3) || ((uintptr_t)d_checker & 3) ||
+  if (n > kMaxRows || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_type & 3) || ((uintptr_t)d_checker & 3) ||
       ((uintptr_t)d_src & 3) || ((uintptr_t)d_nonce & 3) || ((uintptr_t)d_verdict & 3) || ((uintptr_t)d_reply & 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG,
                    "n <= 2^28, 8-byte aligned d_pkts, 4-byte aligned d_type / d_checker / d_src / d_nonce / d_verdict / "

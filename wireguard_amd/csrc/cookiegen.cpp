@@ -16,13 +16,12 @@
 #include <string.h>
 
 #include "../../include/wgcsum.h"
+#include "wgcs_bounds.h"
 #include "wgcs_cookiegen.h"
 
 using namespace wgcs;
 
 namespace {
-
-constexpr uint32_t kMaxRows = 1u << 28, kMaxPeers = 1u << 24;
 
 inline bool pow2_or_0(uint32_t n) { return (n & (n - 1)) == 0; }
 inline bool misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; }

@@ -20,15 +20,6 @@ using namespace wgcs;
 
 namespace {
 
-constexpr uint32_t kMaxRows = 1u << 28;   // rows are counted in 32 bits
-constexpr uint32_t kMaxPeers = 1u << 24;  // as the other per-peer tables
-
-// [a, a + na) and [b, b + nb) share a byte
-bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return na && nb && x < y + nb && y < x + na;
-}
-
 // the checks the two recording calls share: desc is d_start or d_resp
 int check_sent(wgcs_ctx* ctx, const void* desc, const int32_t* d_status, const uint8_t* d_msgs, uint32_t n,
                const wgcs_cookie_gen* d_gen, uint32_t n_peers) {

@@ -11,14 +11,12 @@
 #endif
 
 #include "../../include/wgcsum.h"
+#include "wgcs_bounds.h"
 #include "wgcs_keypairs.h"
 
 using namespace wgcs;
 
 namespace {
-
-constexpr uint32_t kMaxBegin = 1u << 24, kMaxPeers = 1u << 24;  // the key order's bounds (wgcs_keyorder.h)
-constexpr uint32_t kMaxReceived = 1u << 28;
 
 inline bool pow2_or_zero(uint32_t x) { return (x & (x - 1)) == 0; }
 
@@ -26,7 +24,7 @@ bool begin_args_ok(const void* rows, const int32_t* gate, uint32_t n, const wgcs
                    const wgcs_keypairs* kp, const wgcs_session_slot* slots, uint32_t n_slots,
                    const wgcs_session_slot* peer_keys, uint32_t n_peer_slots, const wgcs_aead_key* keys,
                    const uint32_t* key_peer, const int32_t* status) {
-  return n <= kMaxBegin && n_peers <= kMaxPeers && rows && gate && status && gate != status && table && kp && keys &&
+  return n <= kKeyOrderMaxRows && n_peers <= kMaxPeers && rows && gate && status && gate != status && table && kp && keys &&
          key_peer && pow2_or_zero(n_slots) && pow2_or_zero(n_peer_slots) && (!n_slots || slots) &&
          (!n_peer_slots || peer_keys);
 }
@@ -81,7 +79,7 @@ int wgcs_keypairs_received_host(const wgcs_aead_pkt* pkts, const int32_t* verdic
                                 wgcs_session_slot* peer_keys, uint32_t n_peer_slots, wgcs_aead_key* keys,
                                 uint32_t* rotated) {
   if (n == 0) return WGCS_OK;
-  if (n > kMaxReceived || !pkts || !verdict || !rotated || (n_keys && (!key_peer || !keys)) || (n_ids && !peer_rows) ||
+  if (n > kMaxRows || !pkts || !verdict || !rotated || (n_keys && (!key_peer || !keys)) || (n_ids && !peer_rows) ||
       (n_peers && !kp) || !pow2_or_zero(n_slots) || !pow2_or_zero(n_peer_slots) || (n_slots && !slots) ||
       (n_peer_slots && !peer_keys))
     return WGCS_ERR_INVALID_ARG;

@@ -18,8 +18,6 @@ using namespace wgcs;
 
 namespace {
 
-constexpr uint32_t kMaxReceived = 1u << 28;  // rows are counted in 32 bits
-
 // what the two begin forms share: the tail of their argument lists
 int check_begin_tail(wgcs_ctx* ctx, const int32_t* d_gate, uint32_t n, const wgcs_peer_key* d_table, uint32_t n_peers,
                      const wgcs_keypairs* d_kp, const wgcs_session_slot* d_slots, uint32_t n_slots,
@@ -35,17 +33,6 @@ int check_begin_tail(wgcs_ctx* ctx, const int32_t* d_gate, uint32_t n, const wgc
       misaligned(d_slots, 3) || misaligned(d_peer_keys, 3) || misaligned(d_keys, 3) || misaligned(d_key_peer, 3) ||
       misaligned(d_work, 15))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "4-byte aligned tables, 16-byte aligned d_work");
-  return WGCS_OK;
-}
-
-// Carve the workspace and make sure the sort fits it, before anything is enqueued.
-int prepare(wgcs_ctx* ctx, void* d_work, size_t work_bytes, uint32_t n, uint32_t n_peers, hipStream_t s, KeyOrder* ko) {
-  if (!keyorder_carve(d_work, work_bytes, n, ko))
-    return set_err(ctx, WGCS_ERR_INVALID_ARG, "work_bytes %zu is too small for %u rows", work_bytes, n);
-  bool fits = false;
-  const hipError_t e = keyorder_check(*ko, n, n_peers, s, &fits);
-  if (e != hipSuccess) return hip_fail(ctx, e, "key order size query");
-  if (!fits) return set_err(ctx, WGCS_ERR_INVALID_ARG, "work_bytes %zu is too small for %u rows", work_bytes, n);
   return WGCS_OK;
 }
 
@@ -70,7 +57,7 @@ int wgcs_keypairs_begin_responder_batch(wgcs_ctx* ctx, const wgcs_hs_resp* d_res
   hipSetDevice(ctx->device);
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   KeyOrder ko;
-  if (int rc = prepare(ctx, d_work, work_bytes, n, n_peers, s, &ko)) return rc;
+  if (int rc = keyorder_prepare(ctx, d_work, work_bytes, n, n_peers, s, &ko)) return rc;
   const hipError_t e = launch_keypairs_begin_responder(ko, d_resp, d_gate, n, now_ns, d_table, n_peers, d_kp, d_slots,
                                                        n_slots, d_peer_keys, n_peer_slots, d_keys, d_key_peer, n_keys,
                                                        d_status, s);
@@ -99,7 +86,7 @@ int wgcs_keypairs_begin_initiator_batch(wgcs_ctx* ctx, const uint8_t* d_arena, c
   hipSetDevice(ctx->device);
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   KeyOrder ko;
-  if (int rc = prepare(ctx, d_work, work_bytes, n, n_peers, s, &ko)) return rc;
+  if (int rc = keyorder_prepare(ctx, d_work, work_bytes, n, n_peers, s, &ko)) return rc;
   const hipError_t e = launch_keypairs_begin_initiator(ko, d_arena, d_pkts, d_gate, n, now_ns, d_hs_slots, n_hs_slots,
                                                        d_states, n_states, d_table, n_peers, d_kp, d_slots, n_slots,
                                                        d_peer_keys, n_peer_slots, d_keys, d_key_peer, n_keys, d_status,
@@ -117,7 +104,7 @@ int wgcs_keypairs_received_batch(wgcs_ctx* ctx, const wgcs_aead_pkt* d_pkts, con
   if (!d_pkts || !d_verdict || !d_rotated || (n_keys && (!d_key_peer || !d_keys)) || (n_ids && !d_peer_rows) ||
       (n_peers && !d_kp) || (n_slots && !d_slots) || (n_peer_slots && !d_peer_keys))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
-  if (n > kMaxReceived || !pow2_or_0(n_slots) || !pow2_or_0(n_peer_slots) || misaligned(d_pkts, 7) ||
+  if (n > kMaxRows || !pow2_or_0(n_slots) || !pow2_or_0(n_peer_slots) || misaligned(d_pkts, 7) ||
       misaligned(d_verdict, 3) || misaligned(d_rotated, 3) || misaligned(d_key_peer, 3) || misaligned(d_keys, 3) ||
       misaligned(d_peer_rows, 3) || misaligned(d_kp, 3) || misaligned(d_slots, 3) || misaligned(d_peer_keys, 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG,

@@ -3,8 +3,8 @@
 //   begin      the tail of BeginSymmetricSession          device/noise.go:664-722, sessions.go:70-82
 //     kp_begin_resp_keys_kernel / kp_begin_init_keys_kernel   the gate and the stateless checks of every
 //                                descriptor, and its peer row as the key of the key order
-//     kp_begin_resp_groups_kernel / kp_begin_init_groups_kernel   one lane per peer walks that peer's
-//                                descriptors in descriptor order
+//     kp_begin_resp_groups_kernel / kp_begin_init_groups_kernel   the lane walk of wgcs_keyorder.h:
+//                                one lane per peer takes that peer's descriptors in descriptor order
 //   received   ReceivedWithNewKeypair                     noise.go:725-754, receive.go:418-429
 //     kp_received_claim_kernel   the candidates, and the lowest of each peer by atomicMin
 //     kp_received_commit_kernel  the rotation by the rows that hold their claim
@@ -26,9 +26,7 @@ namespace wgcs {
 
 namespace {
 
-constexpr int kThreads = 256;
-
-inline uint32_t blocks_for(uint32_t n) { return (n + kThreads - 1) / kThreads; }
+constexpr int kThreads = kKeyOrderThreads;
 
 // the stateless checks of keypairs_begin, so that a descriptor that fails them joins no peer's run
 __device__ inline bool begin_fields_ok(const uint32_t f[4], uint32_t n_peers, uint32_t n_keys) {
@@ -50,8 +48,7 @@ __global__ __launch_bounds__(kThreads) void kp_begin_resp_keys_kernel(const wgcs
     if (begin_fields_ok(f, n_peers, n_keys)) key = f[0];  // the peer's lane writes the status
   }
   if (key == n_peers) status[j] = st;
-  keys_in[j] = key;
-  slots_in[j] = j;
+  keyorder_put(keys_in, slots_in, j, key);
 }
 
 __global__ __launch_bounds__(kThreads) void kp_begin_init_keys_kernel(
@@ -68,8 +65,7 @@ __global__ __launch_bounds__(kThreads) void kp_begin_init_keys_kernel(
     if (begin_fields_ok(f, n_peers, n_keys)) key = f[0];
   }
   if (key == n_peers) status[q] = st;
-  keys_in[q] = key;
-  slots_in[q] = q;
+  keyorder_put(keys_in, slots_in, q, key);
 }
 
 // Lane h owns the run of the key order that starts at heads[h]: one peer's descriptors, lowest first.
@@ -79,11 +75,8 @@ __global__ __launch_bounds__(kThreads) void kp_begin_resp_groups_kernel(
     const int32_t* __restrict__ gate, int64_t now, const wgcs_peer_key* __restrict__ table, uint32_t n_peers,
     wgcs_keypairs* kp, wgcs_session_slot* d_slots, uint32_t n_slots, wgcs_session_slot* peer_keys,
     uint32_t n_peer_slots, wgcs_aead_key* aead_keys, uint32_t* key_peer, uint32_t n_keys, int32_t* status) {
-  const uint32_t h = blockIdx.x * kThreads + threadIdx.x;
-  if (h >= *n_heads) return;  // <= n
-  const uint32_t p0 = heads[h], key = keys[p0];
-  for (uint32_t p = p0; p < n && keys[p] == key; ++p) {
-    const uint32_t j = slots[p];
+  for (KeyRun r(keys, heads, n_heads, n, blockIdx.x * kThreads + threadIdx.x); r.more(); ++r.p) {
+    const uint32_t j = slots[r.p];
     uint32_t f[4];
     keypairs_responder_fields(resp, gate, j, f);  // taken: the keys kernel saw it so
     status[j] = keypairs_begin(f[0], f[1], f[2], f[3], false, now, table, n_peers, kp, d_slots, n_slots, peer_keys,
@@ -99,11 +92,8 @@ __global__ __launch_bounds__(kThreads) void kp_begin_init_groups_kernel(
     uint32_t n_states, const wgcs_peer_key* __restrict__ table, uint32_t n_peers, wgcs_keypairs* kp,
     wgcs_session_slot* d_slots, uint32_t n_slots, wgcs_session_slot* peer_keys, uint32_t n_peer_slots,
     wgcs_aead_key* aead_keys, uint32_t* key_peer, uint32_t n_keys, int32_t* status) {
-  const uint32_t h = blockIdx.x * kThreads + threadIdx.x;
-  if (h >= *n_heads) return;
-  const uint32_t p0 = heads[h], key = keys[p0];
-  for (uint32_t p = p0; p < n && keys[p] == key; ++p) {
-    const uint32_t q = slots[p];
+  for (KeyRun r(keys, heads, n_heads, n, blockIdx.x * kThreads + threadIdx.x); r.more(); ++r.p) {
+    const uint32_t q = slots[r.p];
     uint32_t f[4];
     // the states are only read: the row answers as it did to the keys kernel
     const int rc = keypairs_initiator_fields(arena, pkts, gate, q, hs_slots, n_hs_slots, states, n_states, f);
@@ -140,12 +130,12 @@ hipError_t launch_keypairs_begin_responder(const KeyOrder& ko, const wgcs_hs_res
                                            wgcs_keypairs* kp, wgcs_session_slot* slots, uint32_t n_slots,
                                            wgcs_session_slot* peer_keys, uint32_t n_peer_slots, wgcs_aead_key* keys,
                                            uint32_t* key_peer, uint32_t n_keys, int32_t* status, hipStream_t s) {
-  hipLaunchKernelGGL(kp_begin_resp_keys_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, s, resp, gate, n, n_peers,
+  hipLaunchKernelGGL(kp_begin_resp_keys_kernel, dim3(keyorder_blocks(n)), dim3(kThreads), 0, s, resp, gate, n, n_peers,
                      n_keys, status, ko.keys_in, ko.slots_in);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if ((e = keyorder_sort(ko, n, n_peers, s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(kp_begin_resp_groups_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, s, ko.keys, ko.slots,
+  hipLaunchKernelGGL(kp_begin_resp_groups_kernel, dim3(keyorder_blocks(n)), dim3(kThreads), 0, s, ko.keys, ko.slots,
                      ko.heads, ko.n_heads, n, resp, gate, now, table, n_peers, kp, slots, n_slots, peer_keys,
                      n_peer_slots, keys, key_peer, n_keys, status);
   return hipGetLastError();
@@ -159,12 +149,12 @@ hipError_t launch_keypairs_begin_initiator(const KeyOrder& ko, const uint8_t* ar
                                            uint32_t n_slots, wgcs_session_slot* peer_keys, uint32_t n_peer_slots,
                                            wgcs_aead_key* keys, uint32_t* key_peer, uint32_t n_keys, int32_t* status,
                                            hipStream_t s) {
-  hipLaunchKernelGGL(kp_begin_init_keys_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, s, arena, pkts, gate, n,
+  hipLaunchKernelGGL(kp_begin_init_keys_kernel, dim3(keyorder_blocks(n)), dim3(kThreads), 0, s, arena, pkts, gate, n,
                      hs_slots, n_hs_slots, states, n_states, n_peers, n_keys, status, ko.keys_in, ko.slots_in);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if ((e = keyorder_sort(ko, n, n_peers, s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(kp_begin_init_groups_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, s, ko.keys, ko.slots,
+  hipLaunchKernelGGL(kp_begin_init_groups_kernel, dim3(keyorder_blocks(n)), dim3(kThreads), 0, s, ko.keys, ko.slots,
                      ko.heads, ko.n_heads, n, arena, pkts, gate, now, hs_slots, n_hs_slots, states, n_states, table,
                      n_peers, kp, slots, n_slots, peer_keys, n_peer_slots, keys, key_peer, n_keys, status);
   return hipGetLastError();
@@ -175,7 +165,7 @@ hipError_t launch_keypairs_received(const wgcs_aead_pkt* pkts, const int32_t* ve
                                     uint32_t n_peers, wgcs_session_slot* slots, uint32_t n_slots,
                                     wgcs_session_slot* peer_keys, uint32_t n_peer_slots, wgcs_aead_key* keys,
                                     uint32_t* rotated, hipStream_t s) {
-  const dim3 grid(blocks_for(n)), block(kThreads);
+  const dim3 grid(keyorder_blocks(n)), block(kThreads);
   hipLaunchKernelGGL(kp_received_claim_kernel, grid, block, 0, s, pkts, verdict, n, key_peer, n_keys, peer_rows, n_ids,
                      kp, n_peers, rotated);
   const hipError_t e = hipGetLastError();

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/wgcsum.h"
+#include "wgcs_bounds.h"
 #include "wgcs_noise.h"
 
 using namespace wgcs;
@@ -64,8 +65,6 @@ void start_of(const uint32_t pub[8], uint32_t hash0[8], uint32_t chain0[8]) {
 }
 
 const uint32_t kBasePoint[8] = {9, 0, 0, 0, 0, 0, 0, 0};
-
-constexpr uint32_t kMaxBatch = 1u << 28;  // rows are counted in 32 bits, as in the device forms
 
 }  // namespace
 
@@ -226,7 +225,7 @@ int wgcs_handshake_initiate_host(const wgcs_hs_start* start, uint32_t n, const u
                                  const wgcs_peer_key* table, uint32_t n_peers, uint32_t n_keys, wgcs_hs_state* states,
                                  uint32_t n_states, uint8_t* msgs, int32_t* status) {
   if (n == 0) return WGCS_OK;
-  if (n > kMaxBatch || !start || !static_public || !msgs || !status || (n_peers && !table) || (n_states && !states))
+  if (n > kMaxRows || !start || !static_public || !msgs || !status || (n_peers && !table) || (n_states && !states))
     return WGCS_ERR_INVALID_ARG;
   for (uint32_t q = 0; q < n; ++q)
     status[q] = noise_initiate_row(start + q, static_public, table, n_peers, n_keys, states, n_states,
@@ -240,7 +239,7 @@ int wgcs_handshake_finish_host(const uint8_t* arena, const wgcs_aead_pkt* pkts, 
                                uint32_t n_states, const uint8_t* psk, uint32_t n_peers, wgcs_aead_key* keys,
                                uint32_t n_keys, uint8_t* work, int32_t* verdict) {
   if (n == 0) return WGCS_OK;
-  if (n > kMaxBatch || (n_slots & (n_slots - 1)) || !arena || !pkts || !type || !responder || !work || !verdict ||
+  if (n > kMaxRows || (n_slots & (n_slots - 1)) || !arena || !pkts || !type || !responder || !work || !verdict ||
       gate == verdict || (n_slots && !slots) || (n_states && !states) || (n_keys && !keys))
     return WGCS_ERR_INVALID_ARG;
   // the two launches of the device form, each a loop: every row sees the states as they stood at the call
@@ -267,7 +266,7 @@ int wgcs_handshake_accept_host(const wgcs_hs_init* init, const int32_t* gate, ui
                                uint32_t n_tickets, wgcs_hs_resp* resp, uint32_t* count, int32_t* verdict) {
   if (!count || (n && (!init || !gate || !verdict)) || (n_tickets && (!tickets || !resp)) ||
       (n && n_peers && (!table || !peers)) || (n && n_ids && !peer_rows) || (n && (const int32_t*)verdict == gate) ||
-      n > kMaxBatch || n_tickets > kMaxBatch)
+      n > kMaxRows || n_tickets > kMaxRows)
     return WGCS_ERR_INVALID_ARG;
   // the passes of the device form, each a loop: every row sees the peer rows as they stood at the call
   for (uint32_t q = 0; q < n; ++q)

@@ -19,12 +19,6 @@
 
 using namespace wgcs;
 
-namespace {
-
-constexpr uint32_t kMaxBatch = 1u << 28;  // rows are counted in 32 bits
-
-}  // namespace
-
 extern "C" {
 
 int wgcs_x25519_batch(wgcs_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_points, uint32_t n, uint8_t* d_out,
@@ -32,7 +26,7 @@ int wgcs_x25519_batch(wgcs_ctx* ctx, const uint8_t* d_scalars, const uint8_t* d_
   if (!ctx) return WGCS_ERR_INVALID_ARG;
   if (n == 0) return WGCS_OK;
   if (!d_scalars || !d_points || !d_out || !d_status) return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
-  if (n > kMaxBatch || ((uintptr_t)d_scalars & 3) || ((uintptr_t)d_points & 3) || ((uintptr_t)d_out & 3) ||
+  if (n > kMaxRows || ((uintptr_t)d_scalars & 3) || ((uintptr_t)d_points & 3) || ((uintptr_t)d_out & 3) ||
       ((uintptr_t)d_status & 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "n <= 2^28, 4-byte aligned d_scalars / d_points / d_out / d_status");
   std::lock_guard<std::mutex> g(ctx->mu);
@@ -51,7 +45,7 @@ int wgcs_handshake_consume_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const wg
   if (!d_arena || !d_pkts || !d_type || !d_responder || !d_verdict || !d_out || (n_peers && !d_table))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
   if (d_gate == d_verdict) return set_err(ctx, WGCS_ERR_INVALID_ARG, "d_verdict must not be d_gate");
-  if (n > kMaxBatch || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_type & 3) || ((uintptr_t)d_gate & 3) ||
+  if (n > kMaxRows || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_type & 3) || ((uintptr_t)d_gate & 3) ||
       ((uintptr_t)d_responder & 3) || ((uintptr_t)d_table & 3) || ((uintptr_t)d_verdict & 3) || ((uintptr_t)d_out & 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG,
                    "n <= 2^28, 8-byte aligned d_pkts, 4-byte aligned d_type / d_gate / d_responder / d_table / "
@@ -71,7 +65,7 @@ int wgcs_handshake_respond_batch(wgcs_ctx* ctx, const wgcs_hs_resp* d_resp, uint
   if (n == 0) return WGCS_OK;
   if (!d_resp || !d_msgs || !d_status || (n_init && !d_init) || (n_peers && !d_table) || (n_keys && !d_keys))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
-  if (n > kMaxBatch || ((uintptr_t)d_resp & 3) || ((uintptr_t)d_init & 3) || ((uintptr_t)d_gate & 3) ||
+  if (n > kMaxRows || ((uintptr_t)d_resp & 3) || ((uintptr_t)d_init & 3) || ((uintptr_t)d_gate & 3) ||
       ((uintptr_t)d_table & 3) || ((uintptr_t)d_psk & 3) || ((uintptr_t)d_keys & 3) || ((uintptr_t)d_msgs & 3) ||
       ((uintptr_t)d_status & 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG,
@@ -91,7 +85,7 @@ int wgcs_handshake_initiate_batch(wgcs_ctx* ctx, const wgcs_hs_start* d_start, u
   if (n == 0) return WGCS_OK;
   if (!d_start || !d_static_public || !d_msgs || !d_status || (n_peers && !d_table) || (n_states && !d_states))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
-  if (n > kMaxBatch || ((uintptr_t)d_start & 3) || ((uintptr_t)d_static_public & 3) || ((uintptr_t)d_table & 3) ||
+  if (n > kMaxRows || ((uintptr_t)d_start & 3) || ((uintptr_t)d_static_public & 3) || ((uintptr_t)d_table & 3) ||
       ((uintptr_t)d_states & 3) || ((uintptr_t)d_msgs & 3) || ((uintptr_t)d_status & 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG,
                    "n <= 2^28, 4-byte aligned d_start / d_static_public / d_table / d_states / d_msgs / d_status");
@@ -114,7 +108,7 @@ int wgcs_handshake_finish_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const wgc
       (n_states && !d_states) || (n_keys && !d_keys))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
   if (d_gate == d_verdict) return set_err(ctx, WGCS_ERR_INVALID_ARG, "d_verdict must not be d_gate");
-  if (n > kMaxBatch || (n_slots & (n_slots - 1)) || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_type & 3) ||
+  if (n > kMaxRows || (n_slots & (n_slots - 1)) || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_type & 3) ||
       ((uintptr_t)d_gate & 3) || ((uintptr_t)d_responder & 3) || ((uintptr_t)d_slots & 3) ||
       ((uintptr_t)d_states & 3) || ((uintptr_t)d_psk & 3) || ((uintptr_t)d_keys & 3) || ((uintptr_t)d_work & 3) ||
       ((uintptr_t)d_verdict & 3))
@@ -139,7 +133,7 @@ int wgcs_handshake_accept_batch(wgcs_ctx* ctx, const wgcs_hs_init* d_init, const
       (n && n_peers && (!d_table || !d_peers)) || (n && n_ids && !d_peer_rows))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
   if (n && (const int32_t*)d_verdict == d_gate) return set_err(ctx, WGCS_ERR_INVALID_ARG, "d_verdict must not be d_gate");
-  if (n > kMaxBatch || n_tickets > kMaxBatch || ((uintptr_t)d_init & 3) || ((uintptr_t)d_gate & 3) ||
+  if (n > kMaxRows || n_tickets > kMaxRows || ((uintptr_t)d_init & 3) || ((uintptr_t)d_gate & 3) ||
       ((uintptr_t)d_table & 3) || ((uintptr_t)d_peer_rows & 3) || ((uintptr_t)d_peers & 3) ||
       ((uintptr_t)d_tickets & 3) || ((uintptr_t)d_resp & 3) || ((uintptr_t)d_count & 3) || ((uintptr_t)d_verdict & 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG,

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/wgcsum.h"
+#include "wgcs_bounds.h"
 #include "wgcs_ratelimit.h"
 
 using namespace wgcs;
@@ -79,8 +80,8 @@ int wgcs_ratelimit_batch_host(const int32_t* gate, const wgcs_src_addr* src, uin
 int wgcs_ratelimit_cleanup_host(const wgcs_rl_entry* old_table, wgcs_rl_entry* new_table, uint32_t n_slots,
                                 int64_t now_ns, uint32_t* live) {
   if (!old_table || !new_table || !live || !rl_slots_ok(n_slots)) return WGCS_ERR_INVALID_ARG;
-  const uintptr_t a = (uintptr_t)old_table, b = (uintptr_t)new_table, bytes = (uintptr_t)n_slots * sizeof *new_table;
-  if (a < b + bytes && b < a + bytes) return WGCS_ERR_INVALID_ARG;  // the two overlap
+  const uint64_t bytes = (uint64_t)n_slots * sizeof *new_table;
+  if (overlap(old_table, bytes, new_table, bytes)) return WGCS_ERR_INVALID_ARG;
   memset(new_table, 0, (size_t)n_slots * sizeof *new_table);
   uint32_t kept = 0;
   for (uint32_t i = 0; i < n_slots; ++i) kept += rl_cleanup_row(i, old_table, new_table, n_slots, now_ns);

@@ -33,16 +33,9 @@ int wgcs_ratelimit_batch(wgcs_ctx* ctx, const int32_t* d_gate, const wgcs_src_ad
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  KeyOrder ko = {};
-  if (n) {
-    // the workspace is carved and the sort sized before anything is enqueued: too small leaves every output untouched
-    bool fits = false;
-    if (!keyorder_carve(d_work, work_bytes, n, &ko))
-      return set_err(ctx, WGCS_ERR_INVALID_ARG, "work_bytes %zu is too small for %u rows", work_bytes, n);
-    const hipError_t e = keyorder_check(ko, n, n_slots, s, &fits);
-    if (e != hipSuccess) return hip_fail(ctx, e, "key order size query");
-    if (!fits) return set_err(ctx, WGCS_ERR_INVALID_ARG, "work_bytes %zu is too small for %u rows", work_bytes, n);
-  }
+  KeyOrder ko = {};  // without rows the launch is the stats memset alone, and nothing is carved
+  if (n)
+    if (int rc = keyorder_prepare(ctx, d_work, work_bytes, n, n_slots, s, &ko)) return rc;
   const hipError_t e = launch_ratelimit(ko, d_gate, d_src, n, d_table, n_slots, now_ns, d_verdict, d_stats, s);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "ratelimit launch");
 }
@@ -53,8 +46,8 @@ int wgcs_ratelimit_cleanup_batch(wgcs_ctx* ctx, const wgcs_rl_entry* d_old, wgcs
   if (!d_old || !d_new || !d_live) return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
   if (!rl_slots_ok(n_slots) || misaligned(d_old, 7) || misaligned(d_new, 7) || misaligned(d_live, 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "n_slots a power of two in [1, 2^24], 8-byte aligned tables");
-  const uintptr_t a = (uintptr_t)d_old, b = (uintptr_t)d_new, bytes = (uintptr_t)n_slots * sizeof(wgcs_rl_entry);
-  if (a < b + bytes && b < a + bytes) return set_err(ctx, WGCS_ERR_INVALID_ARG, "d_new overlaps d_old");
+  const uint64_t bytes = (uint64_t)n_slots * sizeof(wgcs_rl_entry);
+  if (overlap(d_old, bytes, d_new, bytes)) return set_err(ctx, WGCS_ERR_INVALID_ARG, "d_new overlaps d_old");
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
   const hipError_t e =

@@ -39,7 +39,7 @@ namespace wgcs {
 
 namespace {
 
-constexpr int kThreads = 256, kWave = 64;
+constexpr int kThreads = kKeyOrderThreads;
 
 // counts[] of every lane of the block into stats[]: a wave sum, an LDS add per wave, one
 // global atomic per word and block.  Every lane of the block calls it.
@@ -49,9 +49,7 @@ __device__ inline void stats_add(const uint32_t counts[kRlStats], uint32_t* __re
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < kRlStats; ++k) {
-    uint32_t v = counts[k];
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d);
+    const uint32_t v = wave_sum(counts[k]);
     if ((threadIdx.x & (kWave - 1)) == 0 && v) atomicAdd(&sum[k], v);
   }
   __syncthreads();
@@ -99,10 +97,7 @@ __global__ __launch_bounds__(kThreads) void rl_find_kernel(const int32_t* gate, 
       }
     }
   }
-  if (q < n) {
-    keys_in[q] = key;
-    slots_in[q] = q;
-  }
+  if (q < n) keyorder_put(keys_in, slots_in, q, key);
   if (stats) {
     const uint32_t counts[kRlStats] = {0, 0, full ? 1u : 0u, 0};
     stats_add(counts, stats);
@@ -129,8 +124,6 @@ __global__ __launch_bounds__(kThreads) void rl_cleanup_kernel(const wgcs_rl_entr
   if (threadIdx.x == 0 && count) atomicAdd(live, (uint32_t)count);
 }
 
-inline uint32_t blocks_for(uint32_t n) { return (n + kThreads - 1) / kThreads; }
-
 }  // namespace
 
 hipError_t launch_ratelimit(const KeyOrder& ko, const int32_t* gate, const wgcs_src_addr* src, uint32_t n,
@@ -139,11 +132,11 @@ hipError_t launch_ratelimit(const KeyOrder& ko, const int32_t* gate, const wgcs_
   hipError_t e;
   if (stats && (e = hipMemsetAsync(stats, 0, kRlStats * sizeof(uint32_t), s)) != hipSuccess) return e;
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(rl_find_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, s, gate, src, n, table, n_slots, verdict,
+  hipLaunchKernelGGL(rl_find_kernel, dim3(keyorder_blocks(n)), dim3(kThreads), 0, s, gate, src, n, table, n_slots, verdict,
                      ko.keys_in, ko.slots_in, stats);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = keyorder_sort(ko, n, n_slots, s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(rl_position_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, s, ko.keys, ko.slots, n, n_slots, src,
+  hipLaunchKernelGGL(rl_position_kernel, dim3(keyorder_blocks(n)), dim3(kThreads), 0, s, ko.keys, ko.slots, n, n_slots, src,
                      table, now, verdict, stats);
   return hipGetLastError();
 }
@@ -153,7 +146,7 @@ hipError_t launch_ratelimit_cleanup(const wgcs_rl_entry* old_table, wgcs_rl_entr
   hipError_t e = hipMemsetAsync(new_table, 0, (size_t)n_slots * sizeof(wgcs_rl_entry), s);
   if (e != hipSuccess) return e;
   if ((e = hipMemsetAsync(live, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(rl_cleanup_kernel, dim3(blocks_for(n_slots)), dim3(kThreads), 0, s, old_table, new_table, n_slots,
+  hipLaunchKernelGGL(rl_cleanup_kernel, dim3(keyorder_blocks(n_slots)), dim3(kThreads), 0, s, old_table, new_table, n_slots,
                      now, live);
   return hipGetLastError();
 }

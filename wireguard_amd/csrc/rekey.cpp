@@ -14,13 +14,12 @@
 #endif
 
 #include "../../include/wgcsum.h"
+#include "wgcs_bounds.h"
 #include "wgcs_rekey.h"
 
 using namespace wgcs;
 
 namespace {
-
-constexpr uint32_t kMaxRows = 1u << 28, kMaxPeers = 1u << 24;
 
 inline bool rows_ok(const uint32_t* peer_rows, uint32_t n_ids, const wgcs_keypairs* kp, uint32_t n_peers) {
   return (!n_ids || peer_rows) && (!n_peers || kp);

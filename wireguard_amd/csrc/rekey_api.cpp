@@ -21,9 +21,6 @@ using namespace wgcs;
 
 namespace {
 
-constexpr uint32_t kMaxRows = 1u << 28;   // rows are counted in 32 bits
-constexpr uint32_t kMaxPeers = 1u << 24;  // the start call's lanes, and the bound of wgcs_keyorder_work_bytes
-
 // what the lookups of a lane need: id -> row -> keypairs
 int check_rows(wgcs_ctx* ctx, const uint32_t* d_peer_rows, uint32_t n_ids, const wgcs_keypairs* d_kp, uint32_t n_peers) {
   if ((n_ids && !d_peer_rows) || (n_peers && !d_kp)) return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");

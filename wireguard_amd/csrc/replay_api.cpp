@@ -3,6 +3,7 @@
 //   wgcs_replay_batch               keypair.replayFilter.Validate      device/receive.go:414-420
 //   wgcs_send_assign_batch          key and nonces of the send jobs    device/send.go:383-390
 //   wgcs_keyorder_work_bytes        the workspace both batches carve
+//   keyorder_prepare                (wgcs_ctx.h) that carve, for every call on the key order
 // The batches run in replay_kernels.hip on the key order of keyorder.hip; the
 // filters, the send nonces and the workspace are the caller's device memory.
 #include <hip/hip_runtime.h>
@@ -19,24 +20,17 @@
 
 using namespace wgcs;
 
-namespace {
-
-constexpr uint64_t kMaxAssignRows = 1ull << 28;  // rows of the descriptor table are counted in 32 bits
-
-// Carve the workspace and make sure the sort fits it, before anything is
-// enqueued: a workspace that is too small leaves every output untouched.
-int prepare(wgcs_ctx* ctx, void* d_work, size_t work_bytes, uint32_t n, uint32_t n_keys, hipStream_t s, KeyOrder* ko) {
-  if (!d_work || ((uintptr_t)d_work & 15)) return set_err(ctx, WGCS_ERR_INVALID_ARG, "16-byte aligned d_work");
-  if (!keyorder_carve(d_work, work_bytes, n, ko))
-    return set_err(ctx, WGCS_ERR_INVALID_ARG, "work_bytes %zu is too small for %u rows", work_bytes, n);
-  bool fits = false;
-  const hipError_t e = keyorder_check(*ko, n, n_keys, s, &fits);
-  if (e != hipSuccess) return hip_fail(ctx, e, "key order size query");
+int wgcs::keyorder_prepare(wgcs_ctx* ctx, void* d_work, size_t work_bytes, uint32_t n, uint32_t n_keys, hipStream_t s,
+                           KeyOrder* ko) {
+  if (!d_work || misaligned(d_work, 15)) return set_err(ctx, WGCS_ERR_INVALID_ARG, "16-byte aligned d_work");
+  bool fits = keyorder_carve(d_work, work_bytes, n, ko);
+  if (fits) {
+    const hipError_t e = keyorder_check(*ko, n, n_keys, s, &fits);
+    if (e != hipSuccess) return hip_fail(ctx, e, "key order size query");
+  }
   if (!fits) return set_err(ctx, WGCS_ERR_INVALID_ARG, "work_bytes %zu is too small for %u rows", work_bytes, n);
   return WGCS_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -58,15 +52,15 @@ int wgcs_replay_batch(wgcs_ctx* ctx, const wgcs_aead_pkt* d_pkts, const int32_t*
   if (n == 0) return WGCS_OK;
   if (!d_pkts || !d_pkt_len || !d_counter || !d_verdict || (n_keys && !d_filters))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
-  if (n > kKeyOrderMaxRows || n_keys > kKeyOrderMaxKeys || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_counter & 7) ||
-      ((uintptr_t)d_filters & 7) || ((uintptr_t)d_pkt_len & 3) || ((uintptr_t)d_verdict & 3))
+  if (n > kKeyOrderMaxRows || n_keys > kKeyOrderMaxKeys || misaligned(d_pkts, 7) || misaligned(d_counter, 7) ||
+      misaligned(d_filters, 7) || misaligned(d_pkt_len, 3) || misaligned(d_verdict, 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG,
                    "n, n_keys <= 2^24, 8-byte aligned d_pkts / d_counter / d_filters, 4-byte aligned int32 arrays");
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   KeyOrder ko;
-  if (int rc = prepare(ctx, d_work, work_bytes, n, n_keys, s, &ko)) return rc;
+  if (int rc = keyorder_prepare(ctx, d_work, work_bytes, n, n_keys, s, &ko)) return rc;
   const hipError_t e = launch_replay(ko, d_pkts, d_pkt_len, d_counter, n, d_filters, n_keys, limit, d_verdict, s);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "replay launch");
 }
@@ -82,11 +76,11 @@ int wgcs_send_assign_batch(wgcs_ctx* ctx, const int32_t* d_sizes, const uint32_t
       (n_keys && !d_send_nonce))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
   if (n_jobs > kKeyOrderMaxRows || n_keys > kKeyOrderMaxKeys || max_segs == 0 ||
-      (uint64_t)n_jobs * max_segs > kMaxAssignRows)
+      (uint64_t)n_jobs * max_segs > kMaxRows)
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "n_jobs, n_keys <= 2^24, 1 <= max_segs, n_jobs * max_segs <= 2^28");
-  if (((uintptr_t)d_pkts & 7) || ((uintptr_t)d_send_nonce & 7) || ((uintptr_t)d_sizes & 3) || ((uintptr_t)d_peer & 3) ||
-      ((uintptr_t)d_count & 3) || ((uintptr_t)d_status & 3) || ((uintptr_t)d_peer_keys & 3) ||
-      ((uintptr_t)d_nbufs & 3) || ((uintptr_t)d_job_key & 3))
+  if (misaligned(d_pkts, 7) || misaligned(d_send_nonce, 7) || misaligned(d_sizes, 3) || misaligned(d_peer, 3) ||
+      misaligned(d_count, 3) || misaligned(d_status, 3) || misaligned(d_peer_keys, 3) || misaligned(d_nbufs, 3) ||
+      misaligned(d_job_key, 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "8-byte aligned d_pkts / d_send_nonce, 4-byte aligned 32-bit arrays");
   if (n_slots == 0 || (n_slots & (n_slots - 1)))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "n_slots %u is not a power of two", n_slots);
@@ -94,7 +88,7 @@ int wgcs_send_assign_batch(wgcs_ctx* ctx, const int32_t* d_sizes, const uint32_t
   hipSetDevice(ctx->device);
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   KeyOrder ko;
-  if (int rc = prepare(ctx, d_work, work_bytes, n_jobs, n_keys, s, &ko)) return rc;
+  if (int rc = keyorder_prepare(ctx, d_work, work_bytes, n_jobs, n_keys, s, &ko)) return rc;
   const hipError_t e = launch_send_assign(ko, d_sizes, d_peer, d_count, d_status, n_jobs, max_segs, stride, d_peer_keys,
                                           n_slots, d_send_nonce, n_keys, limit, d_pkts, d_nbufs, d_job_key, s);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "send_assign launch");

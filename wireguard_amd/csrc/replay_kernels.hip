@@ -2,10 +2,9 @@
 // device-resident batches (include/wgcsum.h):
 //   replay    keypair.replayFilter.Validate              device/receive.go:414-420, replay/replay.go
 //   assign    keypair.sendNonce.Add(1) and its limit     device/send.go:383-390
-// Both are sequential per key.  Key order (wgcs_keyorder.h) lays the rows of a
-// batch out by key with slot order kept; then one wave owns one key's segment
-// and takes it 64 rows at a trip, every row of a trip decided from the state
-// before the trip, so the wave never walks a segment row by row.
+// Both are sequential per key, and both use the wave walk of wgcs_keyorder.h:
+// every row of a trip is decided from the state before the trip, so the wave
+// never walks a segment row by row.
 //
 // The trip rule of the replay filter, for rows v_0 .. v_{m-1} of one key on the
 // state (L, ring), with ok_i = v_i < limit:
@@ -49,26 +48,10 @@ namespace wgcs {
 
 namespace {
 
-constexpr int kThreads = 256, kWave = 64, kWavesPerBlock = kThreads / kWave;
-constexpr uint32_t kMaxGroupBlocks = 2048;  // the group kernels stride over the segments
+constexpr int kThreads = kKeyOrderThreads, kWavesPerBlock = kKeyOrderWaves;
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 
-__device__ inline uint64_t readlane64(uint64_t x, int lane) {  // lane is wave-uniform
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, lane);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), lane);
-  return ((uint64_t)hi << 32) | lo;
-}
-
 __device__ inline uint64_t max64(uint64_t a, uint64_t b) { return a > b ? a : b; }
-
-// The rows of this trip: positions p .. p + 63 of the key order that still
-// carry `key`.  They are a prefix of the lanes (the order is sorted by key).
-__device__ inline int trip_rows(const uint32_t* __restrict__ keys, uint32_t n, uint64_t p, uint32_t key, int lane,
-                                bool* mine) {
-  const uint64_t pos = p + (uint64_t)lane;
-  *mine = pos < n && keys[pos] == key;
-  return __builtin_amdgcn_readfirstlane(__popcll(__ballot(*mine)));
-}
 
 // ---------------------------------------------------------------------- replay
 // verdict may alias pkt_len: row i is read, then written, by the lane that owns it
@@ -83,16 +66,7 @@ __global__ __launch_bounds__(kThreads) void replay_keys_kernel(const wgcs_aead_p
   // every message that Open decrypted consumes its counter: receive.go:414-420 precedes the trim
   const bool takes = key < n_keys && (len >= 0 || len == WGCS_ERR_PACKET_TOO_SHORT);
   verdict[i] = len;
-  keys_in[i] = takes ? key : n_keys;
-  slots_in[i] = i;
-}
-
-// LDS traffic of one wave to its own ring: program order is execution order on
-// the hardware, so all that is needed is that the compiler keeps it
-__device__ inline void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  keyorder_put(keys_in, slots_in, i, takes ? key : n_keys);
 }
 
 __global__ __launch_bounds__(kThreads) void replay_groups_kernel(const uint32_t* __restrict__ keys,
@@ -105,32 +79,19 @@ __global__ __launch_bounds__(kThreads) void replay_groups_kernel(const uint32_t*
   __shared__ unsigned long long lds_ring[kWavesPerBlock][kReplayBlocks];
   unsigned long long* const ring = lds_ring[threadIdx.x / kWave];
   const int lane = threadIdx.x & (kWave - 1);
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + threadIdx.x / kWave);
-  const uint32_t n_waves = gridDim.x * kWavesPerBlock;
-  const uint32_t nh = *n_heads;  // <= n
-  for (uint32_t h = wave; h < nh; h += n_waves) {
-    const uint32_t p0 = heads[h];
-    const uint32_t key = keys[p0];
-    wgcs_replay_filter* const f = filters + key;
+  for (KeySegments seg(keys, heads, n_heads, n); seg.next();) {
+    wgcs_replay_filter* const f = filters + seg.key;
     uint64_t L = f->last;
     wave_sync();  // the segment before this one has read its ring out
     ring[lane] = f->ring[lane];
     ring[lane + kWave] = f->ring[lane + kWave];
     wave_sync();
-    for (uint64_t p = p0;; p += kWave) {
-      bool mine;
-      const int m = trip_rows(keys, n, p, key, lane, &mine);
-      if (m == 0) break;
-      const uint32_t slot = mine ? slots[p + lane] : 0;
+    seg.trips(lane, [&](bool mine, uint64_t pos, int m) {
+      const uint32_t slot = mine ? slots[pos] : 0;
       const uint64_t v = mine ? counter[slot] : 0;
       const bool ok = mine && v < limit;
       // M_i: an inclusive max scan over the rows that may move `last`, shifted by one lane
-      uint64_t inc = ok ? v : 0;
-#pragma unroll
-      for (int d = 1; d < kWave; d <<= 1) {
-        const uint64_t y = __shfl_up(inc, d);
-        if (lane >= d) inc = max64(inc, y);
-      }
+      const uint64_t inc = wave_scan(ok ? v : 0, lane, WaveMax());
       uint64_t exc = __shfl_up(inc, 1);
       if (lane == 0) exc = 0;
       const uint64_t M = max64(L, exc);
@@ -162,8 +123,7 @@ __global__ __launch_bounds__(kThreads) void replay_groups_kernel(const uint32_t*
       }
       if (mine && !(win && !dup && !old)) verdict[slot] = WGCS_ERR_REPLAY;
       L = Lnew;
-      if (m < kWave) break;
-    }
+    });
     if (lane == 0) f->last = L;
     wave_sync();
     f->ring[lane] = ring[lane];
@@ -189,8 +149,7 @@ __global__ __launch_bounds__(kThreads) void assign_keys_kernel(
       if (k < n_keys) key = k;
     }
   }
-  keys_in[j] = key;
-  slots_in[j] = j;
+  keyorder_put(keys_in, slots_in, j, key);
   nbufs[j] = 0;  // dropped, until the key's wave keeps it
   job_key[j] = kNoKey;
   base[j] = 0;
@@ -206,26 +165,14 @@ __global__ __launch_bounds__(kThreads) void assign_groups_kernel(const uint32_t*
                                                                  uint32_t* __restrict__ job_key,
                                                                  uint64_t* __restrict__ base) {
   const int lane = threadIdx.x & (kWave - 1);
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + threadIdx.x / kWave);
-  const uint32_t n_waves = gridDim.x * kWavesPerBlock;
-  const uint32_t nh = *n_heads;
-  for (uint32_t h = wave; h < nh; h += n_waves) {
-    const uint32_t p0 = heads[h];
-    const uint32_t key = keys[p0];
+  for (KeySegments seg(keys, heads, n_heads, n_jobs); seg.next();) {
+    const uint32_t key = seg.key;
     uint64_t cur = send_nonce[key];
     bool dead = false;  // a job of this key did not fit: send.go:386
-    for (uint64_t p = p0;; p += kWave) {
-      bool mine;
-      const int m = trip_rows(keys, n_jobs, p, key, lane, &mine);
-      if (m == 0) break;
-      const uint32_t j = mine ? slots[p + lane] : 0;
+    seg.trips(lane, [&](bool mine, uint64_t pos, int m) {
+      const uint32_t j = mine ? slots[pos] : 0;
       const uint64_t c = mine ? (uint64_t)count[j] : 0;  // 1 .. max_segs: assign_keys_kernel checked
-      uint64_t inc = c;  // at most 2^24 jobs of < 2^32 each: no wrap
-#pragma unroll
-      for (int d = 1; d < kWave; d <<= 1) {
-        const uint64_t y = __shfl_up(inc, d);
-        if (lane >= d) inc += y;
-      }
+      const uint64_t inc = wave_scan(c, lane, WaveSum());  // at most 2^24 jobs of < 2^32 each: no wrap
       // job j takes [cur + inc - c, cur + inc): it fits iff cur + inc <= limit, without forming the sum
       const uint64_t room = limit > cur ? limit - cur : 0;
       const bool fit = mine && !dead && inc <= room;
@@ -238,8 +185,7 @@ __global__ __launch_bounds__(kThreads) void assign_groups_kernel(const uint32_t*
       }
       if (nofit) dead = true;
       else cur += readlane64(inc, m - 1);
-      if (m < kWave) break;
-    }
+    });
     if (lane == 0) send_nonce[key] = dead ? limit : cur;
   }
 }
@@ -267,24 +213,17 @@ __global__ __launch_bounds__(kThreads) void assign_rows_kernel(const int32_t* __
   pkts[q] = pk;
 }
 
-inline uint32_t blocks_for(uint32_t n) { return (n + kThreads - 1) / kThreads; }
-// a wave per segment, at most n of them
-inline uint32_t group_blocks(uint32_t n) {
-  const uint32_t b = (n + kWavesPerBlock - 1) / kWavesPerBlock;
-  return b < kMaxGroupBlocks ? b : kMaxGroupBlocks;
-}
-
 }  // namespace
 
 hipError_t launch_replay(const KeyOrder& ko, const wgcs_aead_pkt* pkts, const int32_t* pkt_len,
                          const uint64_t* counter, uint32_t n, wgcs_replay_filter* filters, uint32_t n_keys,
                          uint64_t limit, int32_t* verdict, hipStream_t s) {
-  hipLaunchKernelGGL(replay_keys_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, s, pkts, pkt_len, n, n_keys, verdict,
+  hipLaunchKernelGGL(replay_keys_kernel, dim3(keyorder_blocks(n)), dim3(kThreads), 0, s, pkts, pkt_len, n, n_keys, verdict,
                      ko.keys_in, ko.slots_in);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if ((e = keyorder_sort(ko, n, n_keys, s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(replay_groups_kernel, dim3(group_blocks(n)), dim3(kThreads), 0, s, ko.keys, ko.slots, ko.heads,
+  hipLaunchKernelGGL(replay_groups_kernel, dim3(keyorder_group_blocks(n)), dim3(kThreads), 0, s, ko.keys, ko.slots, ko.heads,
                      ko.n_heads, n, counter, limit, filters, verdict);
   return hipGetLastError();
 }
@@ -294,15 +233,15 @@ hipError_t launch_send_assign(const KeyOrder& ko, const int32_t* sizes, const ui
                               const wgcs_session_slot* peer_keys, uint32_t n_slots, uint64_t* send_nonce,
                               uint32_t n_keys, uint64_t limit, wgcs_aead_pkt* pkts, int32_t* nbufs, uint32_t* job_key,
                               hipStream_t s) {
-  hipLaunchKernelGGL(assign_keys_kernel, dim3(blocks_for(n_jobs)), dim3(kThreads), 0, s, count, status, peer, n_jobs,
+  hipLaunchKernelGGL(assign_keys_kernel, dim3(keyorder_blocks(n_jobs)), dim3(kThreads), 0, s, count, status, peer, n_jobs,
                      max_segs, peer_keys, n_slots, n_keys, ko.keys_in, ko.slots_in, nbufs, job_key, ko.base);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if ((e = keyorder_sort(ko, n_jobs, n_keys, s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(assign_groups_kernel, dim3(group_blocks(n_jobs)), dim3(kThreads), 0, s, ko.keys, ko.slots,
+  hipLaunchKernelGGL(assign_groups_kernel, dim3(keyorder_group_blocks(n_jobs)), dim3(kThreads), 0, s, ko.keys, ko.slots,
                      ko.heads, ko.n_heads, n_jobs, count, limit, send_nonce, nbufs, job_key, ko.base);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(assign_rows_kernel, dim3(blocks_for(n_jobs * max_segs)), dim3(kThreads), 0, s, sizes, nbufs,
+  hipLaunchKernelGGL(assign_rows_kernel, dim3(keyorder_blocks(n_jobs * max_segs)), dim3(kThreads), 0, s, sizes, nbufs,
                      job_key, ko.base, n_jobs * max_segs, max_segs, stride, pkts);
   return hipGetLastError();
 }

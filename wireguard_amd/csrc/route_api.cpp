@@ -18,8 +18,6 @@ using namespace wgcs;
 
 namespace {
 
-constexpr uint32_t kMaxBatch = 1u << 28;  // rows are counted in 32 bits
-
 template <typename F>
 int launch(wgcs_ctx* ctx, void* stream, const char* what, F&& f) {
   std::lock_guard<std::mutex> g(ctx->mu);
@@ -46,7 +44,7 @@ int wgcs_recv_classify_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const uint64
   if (!ctx) return WGCS_ERR_INVALID_ARG;
   if (n == 0) return WGCS_OK;
   if (!d_arena || !d_size || !d_slots || !d_pkts || !d_type) return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
-  if (n > kMaxBatch || ((uintptr_t)d_off & 7) || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_size & 3) ||
+  if (n > kMaxRows || ((uintptr_t)d_off & 7) || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_size & 3) ||
       ((uintptr_t)d_slots & 3) || ((uintptr_t)d_type & 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "n <= 2^28, 8-byte aligned d_off / d_pkts, 4-byte aligned d_size / d_slots");
   if (n_slots == 0 || (n_slots & (n_slots - 1)))
@@ -63,7 +61,7 @@ int wgcs_recv_source_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const wgcs_aea
   if (n == 0) return WGCS_OK;
   if (!d_arena || !d_pkts || !d_pkt_len || !d_verdict || (n_keys && !d_key_peer))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
-  if (n > kMaxBatch || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_pkt_len & 3) || ((uintptr_t)d_key_peer & 3) ||
+  if (n > kMaxRows || ((uintptr_t)d_pkts & 7) || ((uintptr_t)d_pkt_len & 3) || ((uintptr_t)d_key_peer & 3) ||
       ((uintptr_t)d_verdict & 3) || ((uintptr_t)d_peer & 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "n <= 2^28, 8-byte aligned d_pkts, 4-byte aligned int32 / uint32 arrays");
   if (int rc = check_image(ctx, d_image, image_bytes)) return rc;
@@ -79,7 +77,7 @@ int wgcs_route_dst_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const uint64_t* 
   if (!ctx) return WGCS_ERR_INVALID_ARG;
   if (n == 0) return WGCS_OK;
   if (!d_arena || !d_size || !d_peer) return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
-  if (n > kMaxBatch || ((uintptr_t)d_off & 7) || ((uintptr_t)d_size & 3) || ((uintptr_t)d_peer & 3))
+  if (n > kMaxRows || ((uintptr_t)d_off & 7) || ((uintptr_t)d_size & 3) || ((uintptr_t)d_peer & 3))
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "n <= 2^28, 8-byte aligned d_off, 4-byte aligned d_size / d_peer");
   if (int rc = check_image(ctx, d_image, image_bytes)) return rc;
   return launch(ctx, stream, "route_dst launch", [&](hipStream_t s) {

@@ -13,13 +13,12 @@
 #include <algorithm>
 
 #include "../../include/wgcsum.h"
+#include "wgcs_bounds.h"
 #include "wgcs_staged.h"
 
 using namespace wgcs;
 
 namespace {
-
-constexpr uint32_t kMaxJobs = 1u << 24, kMaxPeers = 1u << 24;  // the bounds of the device form's key order
 
 inline bool rings_ok(const uint32_t* len, const uint32_t* head, const int32_t* slot_size, const uint8_t* ring,
                      uint32_t n_peers, uint32_t cap, uint64_t stride) {
@@ -40,7 +39,7 @@ int wgcs_staged_stage_host(const uint8_t* arena, uint64_t stride, const int32_t*
   if (!arena || !sizes || !peer || !count || !status_in || !status_out || !job_key || !where || !work ||
       (n_ids && !peer_rows) || (n_peers && !lost) || !rings_ok(len, head, slot_size, ring, n_peers, cap, stride))
     return WGCS_ERR_INVALID_ARG;
-  if (n_jobs > kMaxJobs || max_segs == 0 || (uint64_t)n_jobs * max_segs > kStagedMaxSlots ||
+  if (n_jobs > kKeyOrderMaxRows || max_segs == 0 || (uint64_t)n_jobs * max_segs > kStagedMaxSlots ||
       work_bytes < staged_stage_host_work_bytes(n_jobs) || ((uintptr_t)work & 7))
     return WGCS_ERR_INVALID_ARG;
   uint64_t* const place = (uint64_t*)work;

@@ -30,11 +30,6 @@ int check_rings(wgcs_ctx* ctx, const uint32_t* d_len, const uint32_t* d_head, co
   return WGCS_OK;
 }
 
-inline bool overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
-
 }  // namespace
 
 extern "C" {
@@ -62,16 +57,10 @@ int wgcs_staged_stage_batch(wgcs_ctx* ctx, const uint8_t* d_arena, uint64_t stri
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  // the workspace is carved and the sort sized before anything is enqueued: too small leaves every output untouched
   KeyOrder ko;
-  bool fits = false;
-  if (!keyorder_carve(d_work, work_bytes, n_jobs, &ko))
-    return set_err(ctx, WGCS_ERR_INVALID_ARG, "work_bytes %zu is too small for %u jobs", work_bytes, n_jobs);
-  hipError_t e = keyorder_check(ko, n_jobs, n_peers, s, &fits);
-  if (e != hipSuccess) return hip_fail(ctx, e, "key order size query");
-  if (!fits) return set_err(ctx, WGCS_ERR_INVALID_ARG, "work_bytes %zu is too small for %u jobs", work_bytes, n_jobs);
+  if (int rc = keyorder_prepare(ctx, d_work, work_bytes, n_jobs, n_peers, s, &ko)) return rc;
   const StagedRings st = {d_len, d_head, d_lost, d_slot_size, d_ring, n_peers, cap, stride};
-  e = launch_staged_stage(ko, d_arena, d_sizes, d_peer, d_count, d_status_in, d_status_out, d_job_key, n_jobs, max_segs,
+  const hipError_t e = launch_staged_stage(ko, d_arena, d_sizes, d_peer, d_count, d_status_in, d_status_out, d_job_key, n_jobs, max_segs,
                           d_peer_rows, n_ids, st, d_where, s);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "staged_stage launch");
 }

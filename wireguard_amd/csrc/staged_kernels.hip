@@ -4,8 +4,8 @@
 //     staged_keys_kernel      one lane per slot: d_where's default, and per job its peer row as the
 //                             key, its packets, and the call's count of staged jobs
 //     (the key order of wgcs_keyorder.h over the peer rows)
-//     staged_groups_kernel    one wave per peer: the packets of its jobs summed, the ring words
-//                             written by one lane, every job's place in the ring
+//     staged_groups_kernel    the wave walk, twice per peer: the packets of its jobs summed, the
+//                             ring words written by one lane, then every job's place in the ring
 //     staged_copy_kernel      16 lanes per slot: the scatter copy into the rings
 //   release   SendStagedPackets up to the nonce loop                     send.go:363-426
 //     staged_release_verdict_kernel / _commit_kernel   the weighted form of wgcs_compact.h over the
@@ -35,12 +35,12 @@ namespace wgcs {
 
 namespace {
 
-constexpr int kThreads = kCompactThreads, kWavesPerBlock = kThreads / kWave;
+constexpr int kThreads = kCompactThreads;
+static_assert(kThreads == kKeyOrderThreads, "one block shape for the compacting and the key-order kernels");
 constexpr int kGroup = 16;                             // the lanes that share a packet
 constexpr int kGroupsPerBlock = kThreads / kGroup;
 constexpr int kRowsInFlight = 4;                       // 16-byte rows a lane loads before it stores any
-constexpr uint32_t kMaxGroupBlocks = 2048;             // the groups kernel strides over the peers
-constexpr uint32_t kMaxRingBlocks = 4096;              // and the release copy over the rings
+constexpr uint32_t kMaxRingBlocks = 4096;              // the release copy strides over the rings
 
 // dst[0, size) = src[0, size) by the 16 lanes of a group, l the lane's place in it; both 16-byte aligned
 __device__ inline void copy_packet(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint32_t size,
@@ -64,16 +64,6 @@ __device__ inline void copy_packet(const uint8_t* __restrict__ src, uint8_t* __r
   if (l < (size & 15u)) dst[16 * rows + l] = src[16 * rows + l];
 }
 
-// the inclusive sum of x over the wave's lanes up to this one
-__device__ inline uint32_t wave_scan(uint32_t x, uint32_t lane) {
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d, kWave);
-    if (lane >= (uint32_t)d) x += y;
-  }
-  return x;
-}
-
 // ----------------------------------------------------------------------- stage
 __global__ __launch_bounds__(kThreads) void staged_keys_kernel(
     const int32_t* __restrict__ sizes, const uint32_t* __restrict__ peer, const int32_t* __restrict__ count,
@@ -91,8 +81,7 @@ __global__ __launch_bounds__(kThreads) void staged_keys_kernel(
           staged_job_row(j, peer, count, status_in, status_out, job_key, max_segs, peer_rows, n_ids, n_peers);
       const uint32_t nv = row != WGCS_PEER_NONE ? staged_segs_ok(j, (uint32_t)count[j], sizes, max_segs, stride) : 0;
       staged = nv != 0;
-      keys_in[j] = staged ? row : n_peers;
-      slots_in[j] = j;
+      keyorder_put(keys_in, slots_in, j, staged ? row : n_peers);
       place[j] = nv;  // until the peer's wave turns it into the job's place
     }
   }
@@ -106,36 +95,22 @@ __global__ __launch_bounds__(kThreads) void staged_groups_kernel(
     uint32_t* len, uint32_t* head, uint32_t* lost, uint64_t* place) {
   if (*n_stage == 0) return;
   const uint32_t lane = threadIdx.x & (kWave - 1);
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + threadIdx.x / kWave);
-  const uint32_t n_waves = gridDim.x * kWavesPerBlock;
-  const uint32_t nh = *n_heads;  // <= n_jobs
-  for (uint32_t h = wave; h < nh; h += n_waves) {
-    const uint32_t p0 = heads[h];
-    const uint32_t r = keys[p0];
+  for (KeySegments seg(keys, heads, n_heads, n_jobs); seg.next();) {
+    const uint32_t r = seg.key;
     uint32_t m = 0;  // the packets of the peer's jobs, 64 jobs a trip
-    for (uint64_t p = p0;; p += kWave) {
-      const uint64_t pos = p + lane;
-      const bool mine = pos < n_jobs && keys[pos] == r;
-      const uint64_t rows = __ballot(mine);
-      if (rows == 0) break;
+    seg.trips(lane, [&](bool mine, uint64_t pos, int) {
       const uint32_t nv = mine ? (uint32_t)place[slots[pos]] : 0;
-      m += (uint32_t)__builtin_amdgcn_readlane((int)wave_scan(nv, lane), kWave - 1);
-      if (~rows) break;  // the segment ends inside this trip
-    }
+      m += (uint32_t)__builtin_amdgcn_readlane((int)wave_scan(nv, lane, WaveSum()), kWave - 1);
+    });
     const StagedGroup g = staged_group(len[r], head[r], m, cap);
     uint32_t k0 = 0;  // the rank of the trip's first packet
-    for (uint64_t p = p0;; p += kWave) {
-      const uint64_t pos = p + lane;
-      const bool mine = pos < n_jobs && keys[pos] == r;
-      const uint64_t rows = __ballot(mine);
-      if (rows == 0) break;
+    seg.trips(lane, [&](bool mine, uint64_t pos, int) {
       const uint32_t j = mine ? slots[pos] : 0;
       const uint32_t nv = mine ? (uint32_t)place[j] : 0;
-      const uint32_t inc = wave_scan(nv, lane);
+      const uint32_t inc = wave_scan(nv, lane, WaveSum());
       if (mine) place[j] = staged_place(g, k0 + inc - nv, nv, cap);
       k0 += (uint32_t)__builtin_amdgcn_readlane((int)inc, kWave - 1);
-      if (~rows) break;
-    }
+    });
     if (lane == 0) {
       head[r] = g.head;
       len[r] = g.len;
@@ -226,11 +201,6 @@ __global__ __launch_bounds__(kThreads) void staged_flush_kernel(const uint32_t* 
   if (r < n_peers) staged_flush_row(r, actions, len, head, lost);
 }
 
-inline uint32_t group_blocks(uint32_t n) {  // a wave per peer group, at most n of them
-  const uint32_t b = (n + kWavesPerBlock - 1) / kWavesPerBlock;
-  return b < kMaxGroupBlocks ? b : kMaxGroupBlocks;
-}
-
 }  // namespace
 
 hipError_t launch_staged_stage(const KeyOrder& ko, const uint8_t* arena, const int32_t* sizes, const uint32_t* peer,
@@ -246,7 +216,7 @@ hipError_t launch_staged_stage(const KeyOrder& ko, const uint8_t* arena, const i
                      ko.keys_in, ko.slots_in, ko.base, n_stage, where);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = keyorder_sort(ko, n_jobs, st.n_peers, s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(staged_groups_kernel, dim3(group_blocks(n_jobs)), dim3(kThreads), 0, s, ko.keys, ko.slots, ko.heads,
+  hipLaunchKernelGGL(staged_groups_kernel, dim3(keyorder_group_blocks(n_jobs)), dim3(kThreads), 0, s, ko.keys, ko.slots, ko.heads,
                      ko.n_heads, n_stage, n_jobs, st.cap, st.len, st.head, st.lost, ko.base);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(staged_copy_kernel, dim3((n_rows + kGroupsPerBlock - 1) / kGroupsPerBlock), dim3(kThreads), 0, s,

@@ -22,9 +22,6 @@ using namespace wgcs;
 
 namespace {
 
-constexpr uint32_t kMaxRows = 1u << 28;   // rows are counted in 32 bits
-constexpr uint32_t kMaxPeers = 1u << 24;  // the expire call's lanes, and the bound of wgcs_keyorder_work_bytes
-
 // what the lookups of a lane need: id -> row -> timers
 int check_rows(wgcs_ctx* ctx, const uint32_t* d_peer_rows, uint32_t n_ids, const wgcs_timers* d_timers,
                uint32_t n_peers) {

@@ -26,11 +26,11 @@
 #include <stdint.h>
 
 #include "wgcs_kernels.h"
+#include "wgcs_wave.h"
 
 namespace wgcs {
 
 constexpr int kCompactThreads = 256;
-constexpr int kWave = 64;  // gfx950 runs these kernels in wave64
 constexpr int kScanThreads = 1024;
 
 inline uint32_t compact_blocks(uint32_t n) { return n / kCompactThreads + (n % kCompactThreads != 0); }
@@ -86,9 +86,7 @@ __device__ inline uint32_t compact_rank(bool flag, const uint32_t* __restrict__ 
 __device__ inline void compact_weigh_block(uint32_t w, uint32_t* __restrict__ block_weight) {
   __shared__ uint32_t wave_weight[kCompactThreads / kWave];
   const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  uint32_t x = w;
-#pragma unroll
-  for (int d = kWave / 2; d > 0; d >>= 1) x += __shfl_down(x, d, kWave);
+  const uint32_t x = wave_sum(w);
   if (lane == 0) wave_weight[wave] = x;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -104,12 +102,7 @@ __device__ inline void compact_weigh_block(uint32_t w, uint32_t* __restrict__ bl
 __device__ inline uint32_t compact_weighted_rank(uint32_t w, const uint32_t* __restrict__ below) {
   __shared__ uint32_t wave_weight[kCompactThreads / kWave];
   const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  uint32_t x = w;  // the inclusive sum over the wave's lanes up to this one
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d, kWave);
-    if (lane >= (uint32_t)d) x += y;
-  }
+  const uint32_t x = wave_scan(w, lane, WaveSum());  // the weights of the wave's lanes up to this one
   if (lane == kWave - 1) wave_weight[wave] = x;
   __syncthreads();
   uint32_t rank = 0;

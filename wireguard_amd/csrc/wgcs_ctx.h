@@ -9,9 +9,12 @@
 #include <vector>
 
 #include "../../include/wgcsum.h"
+#include "wgcs_bounds.h"  // kMaxRows, kMaxPeers, overlap
 #include "wgcs_kernels.h"
 
 namespace wgcs {
+
+struct KeyOrder;  // wgcs_keyorder.h
 
 struct DevBuf {
   void* ptr = nullptr;
@@ -28,6 +31,12 @@ inline bool pow2_or_0(uint32_t n) { return (n & (n - 1)) == 0; }
 
 int set_err(wgcs_ctx* ctx, int code, const char* fmt, ...);
 int hip_fail(wgcs_ctx* ctx, hipError_t e, const char* what);
+// What every call on the key order does under ctx->mu before it enqueues anything (replay_api.cpp):
+// d_work is not NULL and 16-byte aligned, *ko is carved out of it for n rows, and the sort's own
+// storage for (n, n_keys) fits the rest.  Not WGCS_OK: the error is set and nothing may be
+// launched, so a workspace that is too small leaves every output untouched.
+int keyorder_prepare(wgcs_ctx* ctx, void* d_work, size_t work_bytes, uint32_t n, uint32_t n_keys, hipStream_t s,
+                     KeyOrder* ko);
 int ensure_dev(wgcs_ctx* ctx, DevBuf& b, size_t bytes);
 int ensure_pinned(wgcs_ctx* ctx, HostBuf& b, size_t bytes);
 // [p, p + n) lies inside one wgcs_host_alloc allocation of ctx (the _locked
