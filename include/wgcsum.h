@@ -1825,8 +1825,10 @@ int wgcs_rekey_start_host(int64_t now_ns, wgcs_rekey *rekey, const wgcs_hs_peer 
  *                    cleared in d_rekey; last_handshake_ns = now_ns                        :279-286
  *
  * The host keeps: index allocation and filling tickets; sending the messages
- * and packets the calls prepared; the endpoint, which it clears when it reads
- * and clears WGCS_TIMERS_CLEAR_SRC; the staged queue (FlushStagedPackets on
+ * and packets the calls prepared (the endpoint and WGCS_TIMERS_CLEAR_SRC are
+ * the wgcs_endpoint_* calls' of the last section, or a host's that keeps the
+ * endpoint itself and clears the source when it reads and clears the bit);
+ * the staged queue (FlushStagedPackets on
  * WGCS_TIMERS_ACT_FLUSH_STAGED, d_staged); handshake.Clear and
  * sessions.Delete(handshake.localIndex) after WGCS_TIMERS_ACT_ZEROED (cookie
  * ageing and ConsumeReply are the wgcs_cookie_*_batch calls of the last
@@ -1850,7 +1852,7 @@ int wgcs_rekey_start_host(int64_t now_ns, wgcs_rekey *rekey, const wgcs_hs_peer 
 
 #define WGCS_TIMERS_ACTIVE 0x1u        /* wgcs_timers.flags: timersActive(); the host's to set */
 #define WGCS_TIMERS_NEED_ANOTHER 0x2u  /* timers.needAnotherKeepalive */
-#define WGCS_TIMERS_CLEAR_SRC 0x4u     /* markEndpointSrcForClearing: the endpoint is the host's, which reads and clears the bit */
+#define WGCS_TIMERS_CLEAR_SRC 0x4u     /* markEndpointSrcForClearing: clearSrcOnTx, which the wgcs_endpoint_set_* and _dst_* calls read and clear */
 #define WGCS_TIMERS_KEEPALIVE_NOW 0x8u /* a SendKeepalive() is owed, receive.go:348; the expire call emits it */
 
 #define WGCS_TIMERS_JITTER_MAX_MS 334u     /* RekeyTimeoutJitterMaxMs, constants.go:24 */
@@ -2411,6 +2413,178 @@ int wgcs_staged_release_host(int64_t now_ns, const wgcs_peer_key *table, const w
                              uint32_t *out_peer, int32_t *out_count, int32_t *out_sizes, int32_t *out_status,
                              uint32_t *n_out, int32_t *status);
 int wgcs_staged_flush_host(const uint32_t *actions, uint32_t *len, uint32_t *head, uint32_t *lost, uint32_t n_peers);
+
+/* ---- the peer endpoints: roaming, sticky source, send destination
+ * (conn/bind.go:308-319, :398-430, conn/sticky.go:46-94, device/peer.go:195-221,
+ * :281-297, device/receive.go:314, :335, :487) ----
+ * peer.endpoint on the device.  A table of wgcs_endpoint rows in the caller's
+ * device memory, row r belonging to d_table[r], holds where each peer is: the
+ * AddrPort its last authentic packet came from and the sticky source
+ * (IP_PKTINFO / IPV6_PKTINFO control message) that packet arrived on.  Beside
+ * it is one uint32_t claim word per row, 0 outside a call as
+ * wgcs_cookie_gen.claim is.  clearSrcOnTx is WGCS_TIMERS_CLEAR_SRC of the
+ * peer's wgcs_timers row, which wgcs_timers_expire_batch sets.
+ *
+ *   recv        the endpoint of every packet slot of a receive batch, and the
+ *               dense address table the screen and the rate limiter take:
+ *               split -> endpoint_recv -> classify -> screen -> ratelimit with
+ *               nothing read back                                bind.go:308-319
+ *   set_*       SetEndpointFromPacket at its three live call sites:
+ *               behind write_build (:487), accept (:314) and finish (:335)
+ *   dst_*       the part of Peer.Send in front of bind.Send: the destination
+ *               of every send job, initiation and response, with ClearSrc
+ *                                                                peer.go:201-211
+ *   coalesce_messages_dst   coalesceMessages with one address family per batch
+ *
+ * Rows are canonical -- zero bytes at and past src_len, zero pad -- so tables
+ * can be compared whole; a row is read and written as sixteen 4-byte words.
+ * The call at receive.go:423 (rotation) needs no call of its own: the
+ * rotating packet is a valid one, so validTailPacket >= its index and :487
+ * overwrites the endpoint in the same container turn.
+ *
+ * The host keeps: turning recvmmsg's Addr into the wgcs_src_addr of each
+ * landed message; the UAPI's peer.endpoint.val = endpoint (uapi.go:325), a
+ * stream-ordered write of a table row; device/sticky.go's route listener, a
+ * stream-ordered OR of WGCS_TIMERS_CLEAR_SRC; txBytes, which it raises by
+ * d_tx_bytes when its send succeeds; and sending.
+ *
+ * Conventions are those of the timers and cookie-generator sections:
+ * asynchronous on stream (NULL: the context's), ordinary launches in blocks of
+ * 256, one lane per row, aligned 4-byte accesses only, nothing allocated, no
+ * clock read, a row count of 0 a no-op.  WGCS_ERR_INVALID_ARG, nothing
+ * written, for a NULL pointer that is needed, a misaligned one (d_timers,
+ * d_pkts, d_groups and d_tx_bytes 8-byte, everything else 4-byte), a count
+ * over its bound (rows 2^28, n_peers 2^24), or where two of a call's tables
+ * and outputs overlap, or one of them and recv's inputs or a set call's d_ep. */
+typedef struct wgcs_endpoint {   /* 64 B, 4-byte aligned */
+  wgcs_src_addr dst;             /* AddrPort; dst.len == 0: no endpoint (peer.endpoint.val == nil) */
+  uint8_t src_len;               /* len(NetEndpoint.src): 0, 32 or 40 */
+  uint8_t pad[3];                /* zero */
+  uint8_t src[40];               /* NetEndpoint.src; zero at and past src_len */
+} wgcs_endpoint;
+#define WGCS_ERR_NO_ENDPOINT (-30) /* "no known endpoint for peer"  peer.go:202-205 */
+
+/* The tail of ReceiveIPvX (bind.go:308-319) over n_batches recvmmsg batches of
+ * n_msgs slots, behind wgcs_split_messages_batch or on its own.  Slot q = b *
+ * n_msgs + s: d_addr[q] is the address recvmmsg left in msgs[s].Addr, d_from is
+ * split's d_src (NULL: every slot carries its own), d_size its d_n_out, and
+ * msgs[s].OOB[:NN] is the d_nn[q] bytes at d_oob + q * oob_stride (oob_stride
+ * a multiple of 4; a d_nn[q] outside [0, oob_stride] reads as no control).
+ *   d_size[q] == 0, or d_from[q] outside [-1, n_msgs)   d_ep[q] all zero
+ *   otherwise   dst = d_addr[q] (d_from[q] == -1) or d_addr[b * n_msgs + d_from[q]], its 20 bytes as
+ *               given; src = getSrcFromControl of slot q's own control buffer
+ * splitMessages moves Addr alone (bind.go:570), so a split packet has the
+ * address of its source message and the sticky source of its own slot.
+ * getSrcFromControl walks the control messages as wgcs_get_gso_size does,
+ * stops at the first IPPROTO_IP/IP_PKTINFO (0/8: 32 bytes) or
+ * IPPROTO_IPV6/IPV6_PKTINFO (41/50: 40 bytes) and leaves its 16 header bytes as
+ * received, then the data from byte 16 on, cut to the room left, zeros behind
+ * a shorter one; a parse error leaves the source empty.  d_addr_out (may be
+ * NULL) gets dst of every slot: wgcs_handshake_screen_batch's and
+ * wgcs_ratelimit_batch's d_src.  n_batches * n_msgs <= 2^28. */
+int wgcs_endpoint_recv_batch(wgcs_ctx *ctx, const wgcs_src_addr *d_addr, const int32_t *d_from, const int32_t *d_size,
+                             const uint8_t *d_oob, uint32_t oob_stride, const int32_t *d_nn, uint32_t n_msgs,
+                             uint32_t n_batches, wgcs_endpoint *d_ep, wgcs_src_addr *d_addr_out, void *stream);
+
+/* SetEndpointFromPacket (peer.go:281-286) over the rows of the call in front;
+ * d_ep is wgcs_endpoint_recv_batch's, n_rows rows.  Two launches: every
+ * candidate raises d_claim[peer row] to its index + 1 by a 32-bit atomic max;
+ * then the holder alone stores the 64 bytes of its source row into
+ * d_table[peer row], clears WGCS_TIMERS_CLEAR_SRC in d_timers[peer row].flags
+ * by an atomic AND and puts the claim back to 0.  The table afterwards is what
+ * taking the rows in ascending order leaves.  A candidate whose source row has
+ * a dst.len that is neither 6 nor 18 is none.  d_ep may not overlap d_table.
+ *   received  :487, behind wgcs_write_build_batch over its n_batches * calls_per_batch rows: a
+ *             row with 0 <= tail < n_rows whose peer id has a row below n_peers takes d_ep[tail]
+ *   accepted  :314, behind wgcs_handshake_accept_batch over its n_tickets descriptors: one with
+ *             init_row < n_rows and peer_row < n_peers takes d_ep[init_row], whatever
+ *             wgcs_handshake_respond_batch answers later (the tail rows carry 0xFFFFFFFF)
+ *   finished  :335, behind wgcs_handshake_finish_batch: row q with d_gate[q] == WGCS_HS_FINISHED
+ *             whose peer row is found as wgcs_timers_finished_batch finds it takes d_ep[q];
+ *             begin's status is not read.  n <= 2^24; n_hs_slots 0 or a power of two */
+int wgcs_endpoint_set_received_batch(wgcs_ctx *ctx, const wgcs_write_group *d_groups, uint32_t n_batches,
+                                     uint32_t calls_per_batch, const wgcs_endpoint *d_ep, uint32_t n_rows,
+                                     const uint32_t *d_peer_rows, uint32_t n_ids, wgcs_endpoint *d_table,
+                                     uint32_t *d_claim, wgcs_timers *d_timers, uint32_t n_peers, void *stream);
+int wgcs_endpoint_set_accepted_batch(wgcs_ctx *ctx, const wgcs_hs_resp *d_resp, uint32_t n_tickets,
+                                     const wgcs_endpoint *d_ep, uint32_t n_rows, wgcs_endpoint *d_table,
+                                     uint32_t *d_claim, wgcs_timers *d_timers, uint32_t n_peers, void *stream);
+int wgcs_endpoint_set_finished_batch(wgcs_ctx *ctx, const uint8_t *d_arena, const wgcs_aead_pkt *d_pkts,
+                                     const int32_t *d_gate, uint32_t n, const wgcs_session_slot *d_hs_slots,
+                                     uint32_t n_hs_slots, const wgcs_hs_state *d_states, uint32_t n_states,
+                                     const wgcs_endpoint *d_ep, wgcs_endpoint *d_table, uint32_t *d_claim,
+                                     wgcs_timers *d_timers, uint32_t n_peers, void *stream);
+
+/* Peer.Send in front of bind.Send (peer.go:201-211).  Entry j:
+ *   takes no part                        d_dst[j] all zero, d_dst_v6[j] = 0, d_dst_status[j] = 0
+ *   its peer row has dst.len == 0        a zero row, 0 and WGCS_ERR_NO_ENDPOINT; the peer's
+ *                                        WGCS_TIMERS_CLEAR_SRC stays (Send returns before it)
+ *   otherwise                            d_dst[j] = the peer's row, with src_len 0 and a zero src if
+ *                                        the peer's WGCS_TIMERS_CLEAR_SRC is set; d_dst_v6[j] = 1 iff
+ *                                        dst.len == 18 (Is6(), v4-mapped included); status 0
+ * and afterwards every such peer whose flag was set has the source of its
+ * table row cleared and the flag too: the result of taking the entries in
+ * order.  Two launches, read and clear, so that no lane reads a row another
+ * lane is clearing.  The outputs may not overlap d_table or d_timers.
+ *   jobs       behind wgcs_aead_seal_batch, in front of coalesce.  Job j takes part by the rule of
+ *              wgcs_timers_sent_batch (kept, status 0, 1 <= count <= max_segs, the peer of
+ *              d_peer[j * max_segs] has a row).  One without an endpoint also gets d_nbufs[j] = 0,
+ *              so coalesce builds no message for it; its nonces are spent, as in the reference.
+ *              d_tx_bytes[j] = the sum of d_lens[j * max_segs + k] (negative: 0) over k < d_nbufs[j]
+ *              (within [0, max_segs]) for a job with a destination, else 0: the operand of
+ *              peer.go:213-218.  n_jobs * max_segs <= 2^28
+ *   initiated  over wgcs_handshake_initiate_batch's d_start and d_status == WGCS_HS_INITIATED
+ *   responded  over wgcs_handshake_respond_batch's d_resp and d_status == WGCS_HS_RESPONDED
+ *              both with peer_row < n_peers, the rule of the two wgcs_cookie_*ed_batch calls */
+int wgcs_endpoint_dst_jobs_batch(wgcs_ctx *ctx, const uint32_t *d_peer, const int32_t *d_count, const int32_t *d_status,
+                                 const uint32_t *d_job_key, uint32_t n_jobs, uint32_t max_segs, const int32_t *d_lens,
+                                 int32_t *d_nbufs, const uint32_t *d_peer_rows, uint32_t n_ids,
+                                 wgcs_endpoint *d_table, wgcs_timers *d_timers, uint32_t n_peers, wgcs_endpoint *d_dst,
+                                 int32_t *d_dst_v6, int32_t *d_dst_status, uint64_t *d_tx_bytes, void *stream);
+int wgcs_endpoint_dst_initiated_batch(wgcs_ctx *ctx, const wgcs_hs_start *d_start, const int32_t *d_status, uint32_t n,
+                                      wgcs_endpoint *d_table, wgcs_timers *d_timers, uint32_t n_peers,
+                                      wgcs_endpoint *d_dst, int32_t *d_dst_v6, int32_t *d_dst_status, void *stream);
+int wgcs_endpoint_dst_responded_batch(wgcs_ctx *ctx, const wgcs_hs_resp *d_resp, const int32_t *d_status, uint32_t n,
+                                      wgcs_endpoint *d_table, wgcs_timers *d_timers, uint32_t n_peers,
+                                      wgcs_endpoint *d_dst, int32_t *d_dst_v6, int32_t *d_dst_status, void *stream);
+
+/* wgcs_coalesce_messages_batch with the address family per batch: batch b
+ * coalesces up to maxIPv6PayloadLen if d_dst_v6[b] != 0, else up to
+ * maxIPv4PayloadLen (bind.go:615-618); d_dst_v6 is wgcs_endpoint_dst_jobs_batch's
+ * and is read once per batch.  A kernel instantiation of its own: the
+ * existing entry runs the code it ran. */
+int wgcs_coalesce_messages_dst_batch(wgcs_ctx *ctx, uint8_t *d_bufs, uint64_t buf_stride, uint32_t buf_cap,
+                                     const int32_t *d_caps, const int32_t *d_lens, const int32_t *d_nbufs,
+                                     uint32_t max_bufs, uint32_t n_batches, const int32_t *d_dst_v6, int32_t *d_n_msgs,
+                                     int32_t *d_msg_first, int32_t *d_msg_len, int32_t *d_msg_gso, void *stream);
+
+/* The seven on host memory, no context and no device, array for array: the
+ * same row functions in the same passes, rows taken in ascending order.
+ * WGCS_ERR_INVALID_ARG, nothing written, for what the device forms refuse. */
+int wgcs_endpoint_recv_host(const wgcs_src_addr *addr, const int32_t *from, const int32_t *size, const uint8_t *oob,
+                            uint32_t oob_stride, const int32_t *nn, uint32_t n_msgs, uint32_t n_batches,
+                            wgcs_endpoint *ep, wgcs_src_addr *addr_out);
+int wgcs_endpoint_set_received_host(const wgcs_write_group *groups, uint32_t n_batches, uint32_t calls_per_batch,
+                                    const wgcs_endpoint *ep, uint32_t n_rows, const uint32_t *peer_rows, uint32_t n_ids,
+                                    wgcs_endpoint *table, uint32_t *claim, wgcs_timers *timers, uint32_t n_peers);
+int wgcs_endpoint_set_accepted_host(const wgcs_hs_resp *resp, uint32_t n_tickets, const wgcs_endpoint *ep,
+                                    uint32_t n_rows, wgcs_endpoint *table, uint32_t *claim, wgcs_timers *timers,
+                                    uint32_t n_peers);
+int wgcs_endpoint_set_finished_host(const uint8_t *arena, const wgcs_aead_pkt *pkts, const int32_t *gate, uint32_t n,
+                                    const wgcs_session_slot *hs_slots, uint32_t n_hs_slots, const wgcs_hs_state *states,
+                                    uint32_t n_states, const wgcs_endpoint *ep, wgcs_endpoint *table, uint32_t *claim,
+                                    wgcs_timers *timers, uint32_t n_peers);
+int wgcs_endpoint_dst_jobs_host(const uint32_t *peer, const int32_t *count, const int32_t *status,
+                                const uint32_t *job_key, uint32_t n_jobs, uint32_t max_segs, const int32_t *lens,
+                                int32_t *nbufs, const uint32_t *peer_rows, uint32_t n_ids, wgcs_endpoint *table,
+                                wgcs_timers *timers, uint32_t n_peers, wgcs_endpoint *dst, int32_t *dst_v6,
+                                int32_t *dst_status, uint64_t *tx_bytes);
+int wgcs_endpoint_dst_initiated_host(const wgcs_hs_start *start, const int32_t *status, uint32_t n,
+                                     wgcs_endpoint *table, wgcs_timers *timers, uint32_t n_peers, wgcs_endpoint *dst,
+                                     int32_t *dst_v6, int32_t *dst_status);
+int wgcs_endpoint_dst_responded_host(const wgcs_hs_resp *resp, const int32_t *status, uint32_t n, wgcs_endpoint *table,
+                                     wgcs_timers *timers, uint32_t n_peers, wgcs_endpoint *dst, int32_t *dst_v6,
+                                     int32_t *dst_status);
 
 #ifdef __cplusplus
 }

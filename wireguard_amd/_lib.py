@@ -45,6 +45,7 @@ ERR_KEY_EXPIRED = -26
 ERR_REKEY_TIMEOUT = -27
 ERR_RATE_LIMITED = -28
 ERR_RATE_TABLE_FULL = -29
+ERR_NO_ENDPOINT = -30
 ERR_HIP = -100
 ERR_NOMEM = -101
 ERR_NO_DEVICE = -102
@@ -326,6 +327,22 @@ def load() -> C.CDLL:
         "wgcs_staged_release_host": ([C.c_int64, vp, vp, vp, u32, u64, vp, vp, vp, vp, vp, u32, u32, u64, u32, vp, vp, vp,
                                       vp, vp, vp, vp], i32),
         "wgcs_staged_flush_host": ([vp, vp, vp, vp, u32], i32),
+        "wgcs_endpoint_recv_batch": ([vp, vp, vp, vp, vp, u32, vp, u32, u32, vp, vp, vp], i32),
+        "wgcs_endpoint_set_received_batch": ([vp, vp, u32, u32, vp, u32, vp, u32, vp, vp, vp, u32, vp], i32),
+        "wgcs_endpoint_set_accepted_batch": ([vp, vp, u32, vp, u32, vp, vp, vp, u32, vp], i32),
+        "wgcs_endpoint_set_finished_batch": ([vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, u32, vp], i32),
+        "wgcs_endpoint_dst_jobs_batch": ([vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp,
+                                          vp], i32),
+        "wgcs_endpoint_dst_initiated_batch": ([vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp], i32),
+        "wgcs_endpoint_dst_responded_batch": ([vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp], i32),
+        "wgcs_coalesce_messages_dst_batch": ([vp, vp, u64, u32, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp], i32),
+        "wgcs_endpoint_recv_host": ([vp, vp, vp, vp, u32, vp, u32, u32, vp, vp], i32),
+        "wgcs_endpoint_set_received_host": ([vp, u32, u32, vp, u32, vp, u32, vp, vp, vp, u32], i32),
+        "wgcs_endpoint_set_accepted_host": ([vp, u32, vp, u32, vp, vp, vp, u32], i32),
+        "wgcs_endpoint_set_finished_host": ([vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, u32], i32),
+        "wgcs_endpoint_dst_jobs_host": ([vp, vp, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp], i32),
+        "wgcs_endpoint_dst_initiated_host": ([vp, vp, u32, vp, vp, u32, vp, vp, vp], i32),
+        "wgcs_endpoint_dst_responded_host": ([vp, vp, u32, vp, vp, u32, vp, vp, vp], i32),
     }
     missing = [name for name in sig if not hasattr(L, name)]
     if missing:

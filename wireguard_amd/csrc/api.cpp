@@ -263,6 +263,7 @@ const char* wgcs_strerror(int status) {
     case WGCS_ERR_REKEY_TIMEOUT: return "within the rekey timeout of the last handshake sent";
     case WGCS_ERR_RATE_LIMITED: return "rate limited: the source address is out of tokens";
     case WGCS_ERR_RATE_TABLE_FULL: return "rate limiter table full: a new source address and no free slot";
+    case WGCS_ERR_NO_ENDPOINT: return "no known endpoint for peer";
     case WGCS_ERR_HIP: return "HIP runtime error";
     case WGCS_ERR_NOMEM: return "out of memory";
     case WGCS_ERR_NO_DEVICE: return "no HIP device";

@@ -3,6 +3,7 @@
 //   wgcs_get_gso_size / wgcs_set_gso_size   getGSOSize / setGSOSize   conn/gso.go:35-100
 //   wgcs_split_messages_batch               splitMessages, device-resident batches  conn/bind.go:542-597
 //   wgcs_coalesce_messages_batch            coalesceMessages, device-resident       conn/bind.go:599-662
+//   wgcs_coalesce_messages_dst_batch        the same, the destination's family per batch
 //   wgcs_split_messages / wgcs_coalesce_messages   the same at Go-call granularity (host buffers)
 // The cmsg helpers only parse / build the few-byte control messages (host
 // data the GPU never sees); every payload byte moves in udp_msgs_kernels.hip.
@@ -15,46 +16,22 @@
 
 #include "../../include/wgcsum.h"
 #include "wgcs_ctx.h"
+#include "wgcs_endpoint.h"
 #include "wgcs_kernels.h"
 
 using namespace wgcs;
 
 namespace {
 
-// golang.org/x/sys/unix (linux/amd64): SizeofCmsghdr 16, 8-byte cmsg alignment.
-constexpr size_t kCmsgHdr = 16;
-inline size_t cmsg_align(size_t n) { return (n + 7) & ~size_t(7); }
-constexpr int kSolUdp = 17, kUdpSegment = 103, kUdpGro = 104;  // linux/udp.h:35-36
-constexpr size_t kSlot = 65536;                                 // staging slot >= MaxMessageSize
+// golang.org/x/sys/unix (linux/amd64): SizeofCmsghdr 16 and the 8-byte cmsg alignment are wgcs_endpoint.h's
+constexpr size_t kCmsgHdr = kCmsgHdrSize;
+constexpr int kSolUdp = kCmsgSolUdp, kUdpSegment = 103;  // linux/udp.h:35
+constexpr size_t kSlot = 65536;                           // staging slot >= MaxMessageSize
 
 inline size_t align16(size_t n) { return (n + 15) & ~size_t(15); }
 
-int parse_gso(const uint8_t* control, size_t len, int* gso) {
-  *gso = 0;
-  size_t off = 0, rlen = len;
-  while (rlen > kCmsgHdr) {  // conn/gso.go:42 (strictly greater)
-    uint64_t hlen;
-    int32_t level, type;
-    memcpy(&hlen, control + off, 8);
-    memcpy(&level, control + off + 8, 4);
-    memcpy(&type, control + off + 12, 4);
-    if (hlen < kCmsgHdr || hlen > rlen) return WGCS_ERR_CMSG;  // ParseOneSocketControlMessage EINVAL
-    if (level == kSolUdp && type == kUdpGro && hlen - kCmsgHdr >= 2) {  // :55-64
-      uint16_t g;
-      memcpy(&g, control + off + kCmsgHdr, 2);
-      *gso = g;
-      return WGCS_OK;
-    }
-    const size_t adv = cmsg_align((size_t)hlen);
-    if (adv < rlen) {
-      off += adv;
-      rlen -= adv;
-    } else {
-      rlen = 0;
-    }
-  }
-  return WGCS_OK;
-}
+// getGSOSize on the control-message walk that getSrcFromControl shares (wgcs_endpoint.h)
+int parse_gso(const uint8_t* control, size_t len, int* gso) { return cmsg_gso_size(control, len, gso); }
 
 void put_gso(uint8_t* control, size_t* len, size_t cap, uint16_t gso) {
   const size_t space = kCmsgHdr + cmsg_align(2);  // CmsgSpace(2)
@@ -119,6 +96,26 @@ int wgcs_coalesce_messages_batch(wgcs_ctx* ctx, uint8_t* d_bufs, uint64_t buf_st
   hipError_t e = launch_udp_coalesce(d_bufs, buf_stride, buf_cap, d_caps, d_lens, d_nbufs, max_bufs, n_batches,
                                      dst_is_v6, d_n_msgs, d_msg_first, d_msg_len, d_msg_gso, s);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "coalesce_messages launch");
+}
+
+int wgcs_coalesce_messages_dst_batch(wgcs_ctx* ctx, uint8_t* d_bufs, uint64_t buf_stride, uint32_t buf_cap,
+                                     const int32_t* d_caps, const int32_t* d_lens, const int32_t* d_nbufs,
+                                     uint32_t max_bufs, uint32_t n_batches, const int32_t* d_dst_v6, int32_t* d_n_msgs,
+                                     int32_t* d_msg_first, int32_t* d_msg_len, int32_t* d_msg_gso, void* stream) {
+  if (!ctx) return WGCS_ERR_INVALID_ARG;
+  if (n_batches == 0 || max_bufs == 0) return WGCS_OK;
+  if (!d_bufs || !d_lens || !d_nbufs || !d_dst_v6 || !d_n_msgs || !d_msg_first || !d_msg_len || !d_msg_gso)
+    return set_err(ctx, WGCS_ERR_INVALID_ARG, "NULL pointer");
+  if ((buf_stride & 15) || ((uintptr_t)d_bufs & 15) || buf_cap > buf_stride || buf_cap > 0x7FFFFFFFu ||
+      misaligned(d_dst_v6, 3))
+    return set_err(ctx, WGCS_ERR_INVALID_ARG,
+                   "16-byte aligned slots with buf_cap <= buf_stride and a 4-byte aligned d_dst_v6 required");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  hipSetDevice(ctx->device);
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipError_t e = launch_udp_coalesce_dst(d_bufs, buf_stride, buf_cap, d_caps, d_lens, d_nbufs, max_bufs, n_batches,
+                                         d_dst_v6, d_n_msgs, d_msg_first, d_msg_len, d_msg_gso, s);
+  return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "coalesce_messages_dst launch");
 }
 
 // splitMessages(msgs, firstMsgAt) (nPackets, err) -- conn/bind.go:542-597.

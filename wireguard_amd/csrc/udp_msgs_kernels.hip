@@ -287,12 +287,19 @@ __global__ __launch_bounds__(256) void udp_split_kernel(const uint8_t* __restric
 // of the block's buffers' destination offset through LDS.  After the barrier
 // a row whose buffer was appended shifts its chunks to the destination phase
 // (previous lane's chunk via DPP row_ror:1 + funnel) and stores them.
-template <int U, int ROWS>
+//
+// Dst is how the destination's family arrives: an int for the whole call
+// (wgcs_coalesce_messages_batch), or a pointer to one int32 per batch
+// (wgcs_coalesce_messages_dst_batch), which wave 0 reads once.
+__device__ __forceinline__ int coalesce_is_v6(int dst_is_v6, uint32_t) { return dst_is_v6; }
+__device__ __forceinline__ int coalesce_is_v6(const int32_t* dst_v6, uint32_t b) { return dst_v6[b]; }
+
+template <int U, int ROWS, class Dst>
 __global__ __launch_bounds__(ROWS * 16) void udp_coalesce_kernel(uint8_t* __restrict__ bufs, uint64_t stride,
                                                             uint32_t buf_cap, const int32_t* __restrict__ caps,
                                                             const int32_t* __restrict__ lens,
                                                             const int32_t* __restrict__ nbufs_arr, uint32_t max_bufs,
-                                                            int dst_is_v6, int32_t* __restrict__ n_msgs_out,
+                                                            Dst dst_is_v6, int32_t* __restrict__ n_msgs_out,
                                                             int32_t* __restrict__ msg_first,
                                                             int32_t* __restrict__ msg_len,
                                                             int32_t* __restrict__ msg_gso) {
@@ -324,7 +331,7 @@ __global__ __launch_bounds__(ROWS * 16) void udp_coalesce_kernel(uint8_t* __rest
 
   // ---- wave 0: the coalescing loop (scalar state over the lengths)
   if (wv == 0) {
-    const int maxp = dst_is_v6 ? kMaxIPv6Payload : kMaxIPv4Payload;  // :615-618
+    const int maxp = coalesce_is_v6(dst_is_v6, b) ? kMaxIPv6Payload : kMaxIPv4Payload;  // :615-618
     int i = -1, npk = 0, gso = 0, end_batch = 0;
     int first = 0, mlen = 0, mcap = 0;
     const bool pub = blockIdx.y == 0;  // one block per batch writes the message table
@@ -449,8 +456,20 @@ hipError_t launch_udp_coalesce(uint8_t* bufs, uint64_t stride, uint32_t buf_cap,
   if (n_batches == 0 || max_bufs == 0) return hipSuccess;
   constexpr int kRows = WGCS_UDP_COAL_ROWS;
   const dim3 grid(n_batches, (max_bufs + kRows - 1) / kRows);
-  hipLaunchKernelGGL((udp_coalesce_kernel<6, kRows>), grid, dim3(kRows * 16), 0, s, bufs, stride, buf_cap, caps, lens, nbufs,
-                     max_bufs, dst_is_v6, n_msgs, msg_first, msg_len, msg_gso);
+  hipLaunchKernelGGL((udp_coalesce_kernel<6, kRows, int>), grid, dim3(kRows * 16), 0, s, bufs, stride, buf_cap, caps, lens,
+                     nbufs, max_bufs, dst_is_v6, n_msgs, msg_first, msg_len, msg_gso);
+  return hipGetLastError();
+}
+
+hipError_t launch_udp_coalesce_dst(uint8_t* bufs, uint64_t stride, uint32_t buf_cap, const int32_t* caps,
+                                   const int32_t* lens, const int32_t* nbufs, uint32_t max_bufs, uint32_t n_batches,
+                                   const int32_t* dst_v6, int32_t* n_msgs, int32_t* msg_first, int32_t* msg_len,
+                                   int32_t* msg_gso, hipStream_t s) {
+  if (n_batches == 0 || max_bufs == 0) return hipSuccess;
+  constexpr int kRows = WGCS_UDP_COAL_ROWS;
+  const dim3 grid(n_batches, (max_bufs + kRows - 1) / kRows);
+  hipLaunchKernelGGL((udp_coalesce_kernel<6, kRows, const int32_t*>), grid, dim3(kRows * 16), 0, s, bufs, stride, buf_cap,
+                     caps, lens, nbufs, max_bufs, dst_v6, n_msgs, msg_first, msg_len, msg_gso);
   return hipGetLastError();
 }
 

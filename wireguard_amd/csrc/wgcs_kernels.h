@@ -49,6 +49,11 @@ hipError_t launch_udp_coalesce(uint8_t* bufs, uint64_t stride, uint32_t buf_cap,
                                const int32_t* lens, const int32_t* nbufs, uint32_t max_bufs, uint32_t n_batches,
                                int dst_is_v6, int32_t* n_msgs, int32_t* msg_first, int32_t* msg_len,
                                int32_t* msg_gso, hipStream_t s);
+// the same with the family of batch b in dst_v6[b]: the kernel's other instantiation
+hipError_t launch_udp_coalesce_dst(uint8_t* bufs, uint64_t stride, uint32_t buf_cap, const int32_t* caps,
+                                   const int32_t* lens, const int32_t* nbufs, uint32_t max_bufs, uint32_t n_batches,
+                                   const int32_t* dst_v6, int32_t* n_msgs, int32_t* msg_first, int32_t* msg_len,
+                                   int32_t* msg_gso, hipStream_t s);
 
 // Transport AEAD, in place (aead_kernels.hip): open != 0 is Open (out_ctr
 // required, mtu unused), else Seal.
@@ -259,5 +264,34 @@ hipError_t launch_staged_release(int64_t now, const wgcs_peer_key* table, const 
                                  int32_t* status, uint32_t* work, hipStream_t s);
 hipError_t launch_staged_flush(const uint32_t* actions, uint32_t* len, uint32_t* head, uint32_t* lost, uint32_t n_peers,
                                hipStream_t s);
+
+// The peer endpoints (endpoint_kernels.hip, the row functions of wgcs_endpoint.h), one lane per
+// row: recv is one launch; a set call is a claim launch and a commit launch, a dst call a read
+// launch and a clear launch, each templated on the finder (wgcs_endpoint.h) that names a row's
+// peer.  The row count of a call is not 0.
+struct EndpointReceived;
+struct EndpointAccepted;
+struct EndpointFinished;
+struct EndpointJobs;
+struct EndpointInitiated;
+struct EndpointResponded;
+hipError_t launch_endpoint_recv(const wgcs_src_addr* addr, const int32_t* from, const int32_t* size, const uint8_t* oob,
+                                uint32_t oob_stride, const int32_t* nn, uint32_t n_msgs, uint32_t n, wgcs_endpoint* ep,
+                                wgcs_src_addr* addr_out, hipStream_t s);
+hipError_t launch_endpoint_set_received(const EndpointReceived& f, uint32_t n, wgcs_endpoint* table, uint32_t* claim,
+                                        wgcs_timers* timers, hipStream_t s);
+hipError_t launch_endpoint_set_accepted(const EndpointAccepted& f, uint32_t n, wgcs_endpoint* table, uint32_t* claim,
+                                        wgcs_timers* timers, hipStream_t s);
+hipError_t launch_endpoint_set_finished(const EndpointFinished& f, uint32_t n, wgcs_endpoint* table, uint32_t* claim,
+                                        wgcs_timers* timers, hipStream_t s);
+hipError_t launch_endpoint_dst_jobs(const EndpointJobs& f, uint32_t n_jobs, const int32_t* lens, int32_t* nbufs,
+                                    wgcs_endpoint* table, wgcs_timers* timers, wgcs_endpoint* dst, int32_t* dst_v6,
+                                    int32_t* dst_status, uint64_t* tx_bytes, hipStream_t s);
+hipError_t launch_endpoint_dst_initiated(const EndpointInitiated& f, uint32_t n, wgcs_endpoint* table,
+                                         wgcs_timers* timers, wgcs_endpoint* dst, int32_t* dst_v6, int32_t* dst_status,
+                                         hipStream_t s);
+hipError_t launch_endpoint_dst_responded(const EndpointResponded& f, uint32_t n, wgcs_endpoint* table,
+                                         wgcs_timers* timers, wgcs_endpoint* dst, int32_t* dst_v6, int32_t* dst_status,
+                                         hipStream_t s);
 
 }  // namespace wgcs
