@@ -60,6 +60,19 @@ static bool scalar(const std::vector<uint8_t>& f, T* out) {
   return true;
 }
 
+// a body of the header for every entry in order, as the host forms run it
+template <class F>
+static void each(const F& f, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) f(i);
+}
+
+// claim, then commit over one source
+template <class Rows>
+static void sent(const Rows& src, const uint8_t* msgs, uint32_t n, wgcs_cookie_gen* g) {
+  each(CookieSentClaim<Rows>{src, g}, n);
+  each(CookieSentCommit<Rows>{src, msgs, g}, n);
+}
+
 int main() {
   std::string line;
   while (std::getline(std::cin, line)) {
@@ -91,14 +104,8 @@ int main() {
                             : wgcs_cookie_initiated_host((const wgcs_hs_start*)desc.p, st, msgs.p, n, g, n_peers);
         if (rc != WGCS_OK) return 4;
       } else {
-        auto row_of = [&](uint32_t j) {
-          return resp ? cookiegen_responded_row(j, (const wgcs_hs_resp*)desc.p, st, n_peers)
-                      : cookiegen_initiated_row(j, (const wgcs_hs_start*)desc.p, st, n_peers);
-        };
-        for (uint32_t j = 0; j < n; ++j) cookiegen_sent_claim(j, row_of(j), g);
-        for (uint32_t j = 0; j < n; ++j)
-          cookiegen_sent_commit(j, row_of(j), resp ? cookiegen_responded_mac1(j, msgs.p) : cookiegen_initiated_mac1(j, msgs.p),
-                                g);
+        if (resp) sent(RespondedRows{(const wgcs_hs_resp*)desc.p, st, n_peers}, msgs.p, n, g);
+        else sent(InitiatedRows{(const wgcs_hs_start*)desc.p, st, n_peers}, msgs.p, n, g);
       }
       print_hex(gen);
     } else if (op == "consume") {
@@ -133,8 +140,8 @@ int main() {
                                      v) != WGCS_OK)
           return 4;
       } else {
-        for (uint32_t q = 0; q < n; ++q) v[q] = cookiegen_open(q, arena.p, pk, ty, t, g, (uint32_t*)work.p);
-        for (uint32_t q = 0; q < n; ++q) cookiegen_commit(q, arena.p, pk, v, t, now, g, ps, (uint32_t*)work.p);
+        each(CookieOpen{arena.p, pk, ty, t, g, (uint32_t*)work.p, v}, n);
+        each(CookieCommit{arena.p, pk, v, t, now, g, ps, (uint32_t*)work.p}, n);
       }
       print_hex(verdict);
       printf(" ");
@@ -151,7 +158,7 @@ int main() {
       if (host) {
         if (wgcs_cookie_age_host(now, (const wgcs_cookie_gen*)gen.p, (wgcs_hs_peer*)peers.p, n_peers) != WGCS_OK) return 4;
       } else {
-        for (uint32_t r = 0; r < n_peers; ++r) cookiegen_age(r, now, (const wgcs_cookie_gen*)gen.p, (wgcs_hs_peer*)peers.p);
+        each(CookieAge{now, (const wgcs_cookie_gen*)gen.p, (wgcs_hs_peer*)peers.p}, n_peers);
       }
       print_hex(peers);
     } else {

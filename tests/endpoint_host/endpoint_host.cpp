@@ -66,11 +66,24 @@ static bool word(const std::vector<uint8_t>& f, uint32_t* out) {
   return true;
 }
 
-template <class Finder>
-static void set_rows(const Finder& f, uint32_t n, const wgcs_endpoint* ep, wgcs_endpoint* table, uint32_t* claim,
-                     wgcs_timers* timers) {
-  for (uint32_t i = 0; i < n; ++i) endpoint_set_claim(i, f.pick(i), claim);
-  for (uint32_t i = 0; i < n; ++i) endpoint_set_commit(i, f.pick(i), ep, table, claim, timers);
+// a body of the header for every entry in order, as the host forms run it
+template <class F>
+static void each(const F& f, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) f(i);
+}
+
+template <class Rows>
+static void set_rows(const Rows& src, uint32_t n, const wgcs_endpoint* ep, uint32_t n_rows, wgcs_endpoint* table,
+                     uint32_t* claim, wgcs_timers* timers) {
+  each(EndpointSetClaim<Rows>{src, ep, n_rows, claim}, n);
+  each(EndpointSetCommit<Rows>{src, ep, n_rows, table, claim, timers}, n);
+}
+
+template <class Rows>
+static void dst_rows(const Rows& src, uint32_t n, wgcs_endpoint* table, wgcs_timers* timers, wgcs_endpoint* dst,
+                     int32_t* dst_v6, int32_t* dst_status) {
+  each(EndpointDstRead<Rows>{src, table, timers, dst, dst_v6, dst_status}, n);
+  each(EndpointDstClear<Rows>{src, table, timers}, n);
 }
 
 int main() {
@@ -103,9 +116,9 @@ int main() {
                                     (wgcs_src_addr*)out.p) != WGCS_OK)
           return 4;
       } else {
-        for (uint32_t q = 0; q < n; ++q)
-          endpoint_recv(q, n_msgs, (const wgcs_src_addr*)addr.p, (const int32_t*)from.p, (const int32_t*)size.p, oob.p,
-                        stride, (const int32_t*)nn.p, (wgcs_endpoint*)ep.p, (wgcs_src_addr*)out.p);
+        each(EndpointRecv{n_msgs, (const wgcs_src_addr*)addr.p, (const int32_t*)from.p, (const int32_t*)size.p, oob.p,
+                          stride, (const int32_t*)nn.p, (wgcs_endpoint*)ep.p, (wgcs_src_addr*)out.p},
+             n);
       }
       print_hex(ep);
       print_hex(out, false);
@@ -131,8 +144,8 @@ int main() {
                                               (const uint32_t*)peer_rows.p, n_ids, t, c, tm, n_peers) != WGCS_OK)
             return 4;
         } else {
-          set_rows(EndpointReceived{(const wgcs_write_group*)groups.p, e, n_rows, (const uint32_t*)peer_rows.p, n_ids, n_peers},
-                   n, e, t, c, tm);
+          set_rows(GroupRows{(const wgcs_write_group*)groups.p, (const uint32_t*)peer_rows.p, n_ids, n_peers}, n, e,
+                   n_rows, t, c, tm);
         }
       } else if (op == "accepted") {
         if (f[0].size() % sizeof(wgcs_hs_resp)) return 3;
@@ -141,7 +154,7 @@ int main() {
         if (host) {
           if (wgcs_endpoint_set_accepted_host((const wgcs_hs_resp*)resp.p, n, e, n_rows, t, c, tm, n_peers) != WGCS_OK) return 4;
         } else {
-          set_rows(EndpointAccepted{(const wgcs_hs_resp*)resp.p, e, n_rows, n_peers}, n, e, t, c, tm);
+          set_rows(AcceptedRows{(const wgcs_hs_resp*)resp.p, n_peers}, n, e, n_rows, t, c, tm);
         }
       } else {
         if (f[1].size() % sizeof(wgcs_aead_pkt) || f[2].size() != f[1].size() / sizeof(wgcs_aead_pkt) * 4 ||
@@ -157,10 +170,10 @@ int main() {
                                               n_st, e, t, c, tm, n_peers) != WGCS_OK)
             return 4;
         } else {
-          set_rows(EndpointFinished{arena.p, (const wgcs_aead_pkt*)pkts.p, (const int32_t*)gate.p,
-                                    (const wgcs_session_slot*)hs_slots.p, n_hs, (const wgcs_hs_state*)states.p, n_st, e,
-                                    n_peers},
-                   n, e, t, c, tm);
+          set_rows(FinishedRows{arena.p, (const wgcs_aead_pkt*)pkts.p, (const int32_t*)gate.p,
+                                (const wgcs_session_slot*)hs_slots.p, n_hs, (const wgcs_hs_state*)states.p, n_st,
+                                n_peers},
+                   n, e, n, t, c, tm);
         }
       }
       print_hex(table);
@@ -187,14 +200,13 @@ int main() {
                                         (int32_t*)v6.p, (int32_t*)ds.p, (uint64_t*)tx.p) != WGCS_OK)
           return 4;
       } else {
-        const EndpointJobs fj = {(const uint32_t*)peer.p, (const int32_t*)count.p, (const int32_t*)status.p,
-                                 (const uint32_t*)key.p, max_segs, (const uint32_t*)peer_rows.p, n_ids, n_peers};
-        for (uint32_t j = 0; j < n; ++j) {
-          const uint32_t row = fj.row(j);
-          endpoint_dst_job(j, row, endpoint_dst_read(j, row, t, tm, (wgcs_endpoint*)dst.p, (int32_t*)v6.p, (int32_t*)ds.p),
-                           max_segs, (const int32_t*)lens.p, (int32_t*)nbufs.p, (uint64_t*)tx.p);
-        }
-        for (uint32_t j = 0; j < n; ++j) endpoint_dst_clear(fj.row(j), t, tm);
+        const KeptJobRows fj = {{(const uint32_t*)peer.p, (const int32_t*)count.p, (const int32_t*)status.p, max_segs,
+                                 (const uint32_t*)peer_rows.p, n_ids, n_peers},
+                                (const uint32_t*)key.p};
+        each(EndpointDstJobs{{fj, t, tm, (wgcs_endpoint*)dst.p, (int32_t*)v6.p, (int32_t*)ds.p}, (const int32_t*)lens.p,
+                             (int32_t*)nbufs.p, (uint64_t*)tx.p},
+             n);
+        each(EndpointDstClear<KeptJobRows>{fj, t, tm}, n);
       }
       print_hex(dst);
       print_hex(v6);
@@ -222,11 +234,10 @@ int main() {
                                                                (wgcs_endpoint*)dst.p, (int32_t*)v6.p, (int32_t*)ds.p);
         if (rc != WGCS_OK) return 4;
       } else {
-        const EndpointResponded fr = {(const wgcs_hs_resp*)desc.p, st, n_peers};
-        const EndpointInitiated fi = {(const wgcs_hs_start*)desc.p, st, n_peers};
-        for (uint32_t j = 0; j < n; ++j)
-          endpoint_dst_read(j, resp ? fr.row(j) : fi.row(j), t, tm, (wgcs_endpoint*)dst.p, (int32_t*)v6.p, (int32_t*)ds.p);
-        for (uint32_t j = 0; j < n; ++j) endpoint_dst_clear(resp ? fr.row(j) : fi.row(j), t, tm);
+        wgcs_endpoint* const d = (wgcs_endpoint*)dst.p;
+        int32_t *const d6 = (int32_t*)v6.p, *const dstat = (int32_t*)ds.p;
+        if (resp) dst_rows(RespondedRows{(const wgcs_hs_resp*)desc.p, st, n_peers}, n, t, tm, d, d6, dstat);
+        else dst_rows(InitiatedRows{(const wgcs_hs_start*)desc.p, st, n_peers}, n, t, tm, d, d6, dstat);
       }
       print_hex(dst);
       print_hex(v6);

@@ -67,6 +67,12 @@ static bool scalar(const std::vector<uint8_t>& f, T* out) {
   return true;
 }
 
+// a body of the header for every entry in order, as the host forms run it
+template <class F>
+static void each(const F& f, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) f(i);
+}
+
 int main() {
   std::string line;
   while (std::getline(std::cin, line)) {
@@ -97,8 +103,7 @@ int main() {
       if (host) {
         if (wgcs_rekey_recv_gate_host(p, n, now, kpr, n_keys, pr, n_ids, k, n_peers) != 0) return 3;
       } else {
-        for (uint32_t i = 0; i < n; ++i)
-          if (rekey_recv_expired(i, p, now, kpr, n_keys, pr, n_ids, k, n_peers)) p[i].key = WGCS_SESSION_EXPIRED;
+        each(RekeyRecvGate{{p, kpr, n_keys, pr, n_ids, n_peers}, now, k, p}, n);
       }
       outs = {pkts};
     } else if (op == "gate" || op == "sent") {
@@ -130,8 +135,7 @@ int main() {
           if (wgcs_rekey_send_gate_host(pe, c, st, n, max_segs, now, pr, n_ids, k, n_peers, sn, n_keys, limit, rk, so) != 0)
             return 3;
         } else {
-          for (uint32_t j = 0; j < n; ++j)
-            so[j] = rekey_send_gate(j, pe, c, st, max_segs, now, pr, n_ids, k, n_peers, sn, n_keys, limit, rk);
+          each(RekeySendGate{{pe, c, st, max_segs, pr, n_ids, n_peers}, now, k, sn, n_keys, limit, rk, so}, n);
         }
         outs = {out, rekey};
       } else {
@@ -140,8 +144,7 @@ int main() {
           if (wgcs_rekey_sent_host(pe, c, st, jk, n, max_segs, now, pr, n_ids, k, n_peers, sn, n_keys, limit, rk) != 0)
             return 3;
         } else {
-          for (uint32_t j = 0; j < n; ++j)
-            rekey_sent(j, pe, c, st, jk, max_segs, now, pr, n_ids, k, n_peers, sn, n_keys, limit, rk);
+          each(RekeySent{{pe, c, st, max_segs, pr, n_ids, n_peers}, jk, now, k, sn, n_keys, limit, rk}, n);
         }
         outs = {rekey};
       }
@@ -162,7 +165,7 @@ int main() {
       if (host) {
         if (wgcs_rekey_received_host(g, n / cpb, cpb, now, pr, n_ids, k, n_peers, rk) != 0) return 3;
       } else {
-        for (uint32_t c = 0; c < n; ++c) rekey_received(c, g, now, pr, n_ids, k, n_peers, rk);
+        each(RekeyReceived{{g, pr, n_ids, n_peers}, now, k, rk}, n);
       }
       outs = {rekey};
     } else if (op == "resp") {
@@ -177,7 +180,7 @@ int main() {
       if (host) {
         if (wgcs_rekey_responded_host(r, g, n, now, rk, n_peers) != 0) return 3;
       } else {
-        for (uint32_t j = 0; j < n; ++j) rekey_responded(j, r, g, now, rk, n_peers);
+        each(RekeyResponded{{r, g, n_peers}, now, rk}, n);
       }
       outs = {rekey};
     } else if (op == "start") {

@@ -1,4 +1,4 @@
-"""The row functions of wireguard_amd/csrc/wgcs_cookiegen.h (claim and commit of
+"""The bodies of wireguard_amd/csrc/wgcs_cookiegen.h (claim and commit of
 lastMAC1, open and commit of cookie replies, the ageing row) and the host forms
 of cookiegen.cpp as host code under AddressSanitizer + UBSan (CPU only).
 

@@ -1,5 +1,5 @@
-"""The row functions of wireguard_amd/csrc/wgcs_endpoint.h (the control-message
-walk, one slot's endpoint, the finders, claim and commit, read and clear) and the
+"""The bodies of wireguard_amd/csrc/wgcs_endpoint.h (the control-message walk,
+one slot's endpoint, claim and commit, read and clear over the sources of wgcs_events.h) and the
 host forms of endpoint.cpp as host code under AddressSanitizer + UBSan (CPU only).
 
 tests/endpoint_host/endpoint_host.cpp is a stand-alone program with its own main

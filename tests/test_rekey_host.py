@@ -1,5 +1,5 @@
-"""The row functions of wireguard_amd/csrc/wgcs_rekey.h (rekey_recv_expired,
-rekey_send_gate, rekey_sent, rekey_received, rekey_responded and the three
+"""The bodies and row functions of wireguard_amd/csrc/wgcs_rekey.h (RekeyRecvGate,
+RekeySendGate, RekeySent, RekeyReceived, RekeyResponded and the three
 passes of the start call) and the host forms of rekey.cpp as host code under
 AddressSanitizer + UBSan (CPU only).
 

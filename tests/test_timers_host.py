@@ -1,4 +1,4 @@
-"""The row functions of wireguard_amd/csrc/wgcs_timers.h (the six event rows and
+"""The bodies and row functions of wireguard_amd/csrc/wgcs_timers.h (the six event rows and
 the three passes of the expire call) and the host forms of timers.cpp as host
 code under AddressSanitizer + UBSan (CPU only).
 

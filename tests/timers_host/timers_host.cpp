@@ -71,6 +71,12 @@ static bool scalar(const std::vector<uint8_t>& f, T* out) {
   return true;
 }
 
+// a body of the header for every entry in order, as the host forms run it
+template <class F>
+static void each(const F& f, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) f(i);
+}
+
 int main() {
   std::string line;
   while (std::getline(std::cin, line)) {
@@ -108,7 +114,7 @@ int main() {
       if (host) {
         if (wgcs_timers_sent_host(sz, pe, c, st, jk, n, max_segs, now, seed, pr, n_ids, tm, n_peers) != 0) return 3;
       } else {
-        for (uint32_t j = 0; j < n; ++j) timers_sent(j, sz, pe, c, st, jk, max_segs, now, seed, pr, n_ids, tm, n_peers);
+        each(TimersSent{{{pe, c, st, max_segs, pr, n_ids, n_peers}, jk}, sz, now, seed, tm}, n);
       }
       outs = {timers};
     } else if (op == "rcvd") {
@@ -126,7 +132,7 @@ int main() {
       if (host) {
         if (wgcs_timers_received_host(g, n / cpb, cpb, now, pr, n_ids, tm, n_peers) != 0) return 3;
       } else {
-        for (uint32_t c = 0; c < n; ++c) timers_received(c, g, now, pr, n_ids, tm, n_peers);
+        each(TimersReceived{{g, pr, n_ids, n_peers}, now, tm}, n);
       }
       outs = {timers};
     } else if (op == "init") {
@@ -143,8 +149,8 @@ int main() {
       if (host) {
         if (wgcs_timers_initiated_host(why, sp, st, n_tickets, now, seed, tm, n_peers) != 0) return 3;
       } else {
-        for (uint32_t r = 0; r < n_peers; ++r) timers_initiated_fresh(r, why, tm);
-        for (uint32_t k = 0; k < n_tickets; ++k) timers_initiated(k, sp, st, now, seed, tm, n_peers);
+        each(TimersFresh{why, tm}, n_peers);
+        each(TimersInitiated{{sp, st, n_peers}, now, seed, tm}, n_tickets);
       }
       outs = {timers};
     } else if (op == "resp") {
@@ -159,7 +165,7 @@ int main() {
       if (host) {
         if (wgcs_timers_responded_host(r, g, n, now, tm, n_peers) != 0) return 3;
       } else {
-        for (uint32_t j = 0; j < n; ++j) timers_responded(j, r, g, now, tm, n_peers);
+        each(TimersResponded{{r, g, n_peers}, now, tm}, n);
       }
       outs = {timers};
     } else if (op == "fin") {
@@ -184,7 +190,7 @@ int main() {
       if (host) {
         if (wgcs_timers_finished_host(arena->p, pk, g, b, n, now, hs, n_hs, st, n_states, tm, rk, n_peers) != 0) return 3;
       } else {
-        for (uint32_t q = 0; q < n; ++q) timers_finished(q, arena->p, pk, g, b, now, hs, n_hs, st, n_states, tm, rk, n_peers);
+        each(TimersFinished{{arena->p, pk, g, hs, n_hs, st, n_states, n_peers}, b, now, tm, rk}, n);
       }
       outs = {timers, rekey};
     } else if (op == "rot") {
@@ -205,7 +211,7 @@ int main() {
       if (host) {
         if (wgcs_timers_rotated_host(pk, ro, n, now, kpr, n_keys, pr, n_ids, tm, rk, n_peers) != 0) return 3;
       } else {
-        for (uint32_t i = 0; i < n; ++i) timers_rotated(i, pk, ro, now, kpr, n_keys, pr, n_ids, tm, rk, n_peers);
+        each(TimersRotated{{pk, kpr, n_keys, pr, n_ids, n_peers}, ro, now, tm, rk}, n);
       }
       outs = {timers, rekey};
     } else if (op == "exp") {

@@ -164,7 +164,8 @@ def main() -> None:
                                   "host_one_core": {"us_per_reply": round(host_us, 3), "replies": count,
                                                     "path": "wgcs_cookie_consume_reply, one ctypes call per reply",
                                                     "device_over_host": round(n / us * host_us, 1)},
-                                  "kernel": "cookie_open_kernel + cookie_commit_kernel", "timing": timing}), flush=True)
+                                  "kernel": "each_kernel<CookieOpen> + each_kernel<CookieCommit>", "timing": timing}),
+                      flush=True)
         return
 
     if args.mode == "sent":
@@ -194,8 +195,8 @@ def main() -> None:
             print(json.dumps({**base, "metric": "cookie_initiated_us", "unit": "us", "rows": n, "peers": P,
                               "value": med(rounds, 0), "cookie_initiated_us": [r[0] for r in rounds],
                               "timers_initiated_us_same_tickets": [r[1] for r in rounds],
-                              "kernel": "cookie_sent_claim_kernel + cookie_sent_commit_kernel (two launches, as "
-                                        "timers_initiated's two)", "timing": timing}), flush=True)
+                              "kernel": "each_kernel<CookieSentClaim> + each_kernel<CookieSentCommit> (two launches, "
+                                        "as timers_initiated's two)", "timing": timing}), flush=True)
         return
 
     w = make_world(P)

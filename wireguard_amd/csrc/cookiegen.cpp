@@ -5,9 +5,9 @@
 //   wgcs_cookie_responded_host     lastMAC1 behind respond                cookie.go:301-302
 //   wgcs_cookie_consume_host       cookie replies of a receive batch      device/receive.go:246-269, cookie.go:319-339
 //   wgcs_cookie_age_host           CookieRefreshTime                      cookie.go:306
-// They run the row functions of wgcs_cookiegen.h, the code the lanes of
-// cookiegen_kernels.hip run, taken in row order, in the passes of the device
-// form.  Plain C++: the host test program (tests/cookiegen_host/cookiegen_host.cpp)
+// They run the bodies of wgcs_cookiegen.h, the code the lanes of the device
+// forms run, taken in row order, in the passes of the device form.  Plain C++:
+// the host test program (tests/cookiegen_host/cookiegen_host.cpp)
 // links this file as it is.
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>  // the library's build compiles every file as HIP: WGCS_HD's qualifiers
@@ -23,13 +23,21 @@ using namespace wgcs;
 
 namespace {
 
-inline bool pow2_or_0(uint32_t n) { return (n & (n - 1)) == 0; }
 inline bool misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; }
 
 inline bool sent_ok(const void* desc, const int32_t* status, const uint8_t* msgs, uint32_t n, const wgcs_cookie_gen* gen,
                     uint32_t n_peers) {
   return desc && status && msgs && (!n_peers || gen) && n <= kMaxRows && n_peers <= kMaxPeers && !misaligned4(desc) &&
          !misaligned4(status) && !misaligned4(msgs) && !misaligned4(gen);
+}
+
+// the launches of the device form, each a loop: the claims, then the commits
+template <class Rows>
+void sent_rows(const Rows& src, const uint8_t* msgs, uint32_t n, wgcs_cookie_gen* gen) {
+  const CookieSentClaim<Rows> claim = {src, gen};
+  const CookieSentCommit<Rows> commit = {src, msgs, gen};
+  for (uint32_t j = 0; j < n; ++j) claim(j);
+  for (uint32_t j = 0; j < n; ++j) commit(j);
 }
 
 }  // namespace
@@ -53,10 +61,7 @@ int wgcs_cookie_initiated_host(const wgcs_hs_start* start, const int32_t* status
                                wgcs_cookie_gen* gen, uint32_t n_peers) {
   if (n == 0) return WGCS_OK;
   if (!sent_ok(start, status, msgs, n, gen, n_peers)) return WGCS_ERR_INVALID_ARG;
-  // the launches of the device form, each a loop: the claims, then the commits
-  for (uint32_t j = 0; j < n; ++j) cookiegen_sent_claim(j, cookiegen_initiated_row(j, start, status, n_peers), gen);
-  for (uint32_t j = 0; j < n; ++j)
-    cookiegen_sent_commit(j, cookiegen_initiated_row(j, start, status, n_peers), cookiegen_initiated_mac1(j, msgs), gen);
+  sent_rows(InitiatedRows{start, status, n_peers}, msgs, n, gen);
   return WGCS_OK;
 }
 
@@ -64,9 +69,7 @@ int wgcs_cookie_responded_host(const wgcs_hs_resp* resp, const int32_t* status, 
                                wgcs_cookie_gen* gen, uint32_t n_peers) {
   if (n == 0) return WGCS_OK;
   if (!sent_ok(resp, status, msgs, n, gen, n_peers)) return WGCS_ERR_INVALID_ARG;
-  for (uint32_t j = 0; j < n; ++j) cookiegen_sent_claim(j, cookiegen_responded_row(j, resp, status, n_peers), gen);
-  for (uint32_t j = 0; j < n; ++j)
-    cookiegen_sent_commit(j, cookiegen_responded_row(j, resp, status, n_peers), cookiegen_responded_mac1(j, msgs), gen);
+  sent_rows(RespondedRows{resp, status, n_peers}, msgs, n, gen);
   return WGCS_OK;
 }
 
@@ -86,15 +89,18 @@ int wgcs_cookie_consume_host(const uint8_t* arena, const wgcs_aead_pkt* pkts, co
                              n_ids,    n_peers};
   uint32_t* const w = (uint32_t*)work;
   // the launches of the device form, each a loop: open and claim, then commit
-  for (uint32_t q = 0; q < n; ++q) verdict[q] = cookiegen_open(q, arena, pkts, type, t, gen, w);
-  for (uint32_t q = 0; q < n; ++q) cookiegen_commit(q, arena, pkts, verdict, t, now_ns, gen, peers, w);
+  const CookieOpen open = {arena, pkts, type, t, gen, w, verdict};
+  const CookieCommit commit = {arena, pkts, verdict, t, now_ns, gen, peers, w};
+  for (uint32_t q = 0; q < n; ++q) open(q);
+  for (uint32_t q = 0; q < n; ++q) commit(q);
   return WGCS_OK;
 }
 
 int wgcs_cookie_age_host(int64_t now_ns, const wgcs_cookie_gen* gen, wgcs_hs_peer* peers, uint32_t n_peers) {
   if (n_peers == 0) return WGCS_OK;
   if (!gen || !peers || n_peers > kMaxPeers || misaligned4(gen) || misaligned4(peers)) return WGCS_ERR_INVALID_ARG;
-  for (uint32_t r = 0; r < n_peers; ++r) cookiegen_age(r, now_ns, gen, peers);
+  const CookieAge age = {now_ns, gen, peers};
+  for (uint32_t r = 0; r < n_peers; ++r) age(r);
   return WGCS_OK;
 }
 

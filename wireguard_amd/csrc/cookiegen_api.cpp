@@ -4,8 +4,8 @@
 //   wgcs_cookie_responded_batch    lastMAC1 behind respond            cookie.go:301-302
 //   wgcs_cookie_consume_batch      cookie replies of a receive batch  device/receive.go:246-269, cookie.go:319-339
 //   wgcs_cookie_age_batch          CookieRefreshTime                  cookie.go:306
-// They run in cookiegen_kernels.hip; every table and the consume call's scratch
-// are the caller's device memory.  The host functions of the same section are
+// They run the bodies of wgcs_cookiegen.h through launch_each; every table and
+// the consume call's scratch are the caller's device memory.  The host functions of the same section are
 // in cookiegen.cpp.
 #include <hip/hip_runtime.h>
 
@@ -45,8 +45,10 @@ int wgcs_cookie_initiated_batch(wgcs_ctx* ctx, const wgcs_hs_start* d_start, con
   if (n_peers == 0) return WGCS_OK;  // no row to write
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e =
-      launch_cookie_initiated(d_start, d_status, d_msgs, n, d_gen, n_peers, stream ? (hipStream_t)stream : ctx->stream);
+  const InitiatedRows src = {d_start, d_status, n_peers};
+  const hipError_t e = launch_each(CookieSentClaim<InitiatedRows>{src, d_gen},
+                                   CookieSentCommit<InitiatedRows>{src, d_msgs, d_gen}, n,
+                                   stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "cookie_initiated launch");
 }
 
@@ -61,8 +63,10 @@ int wgcs_cookie_responded_batch(wgcs_ctx* ctx, const wgcs_hs_resp* d_resp, const
   if (n_peers == 0) return WGCS_OK;  // no row to write
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e =
-      launch_cookie_responded(d_resp, d_status, d_msgs, n, d_gen, n_peers, stream ? (hipStream_t)stream : ctx->stream);
+  const RespondedRows src = {d_resp, d_status, n_peers};
+  const hipError_t e = launch_each(CookieSentClaim<RespondedRows>{src, d_gen},
+                                   CookieSentCommit<RespondedRows>{src, d_msgs, d_gen}, n,
+                                   stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "cookie_responded launch");
 }
 
@@ -94,8 +98,10 @@ int wgcs_cookie_consume_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const wgcs_
                              d_key_peer, n_keys,     d_peer_rows, n_ids,  n_peers};
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_cookie_consume(d_arena, d_pkts, d_type, n, now_ns, t, d_gen, d_peers, (uint32_t*)d_work,
-                                             d_verdict, stream ? (hipStream_t)stream : ctx->stream);
+  uint32_t* const work = (uint32_t*)d_work;
+  const hipError_t e = launch_each(CookieOpen{d_arena, d_pkts, d_type, t, d_gen, work, d_verdict},
+                                   CookieCommit{d_arena, d_pkts, d_verdict, t, now_ns, d_gen, d_peers, work}, n,
+                                   stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "cookie_consume launch");
 }
 
@@ -110,7 +116,8 @@ int wgcs_cookie_age_batch(wgcs_ctx* ctx, int64_t now_ns, const wgcs_cookie_gen* 
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "d_gen overlaps d_peers");
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_cookie_age(now_ns, d_gen, d_peers, n_peers, stream ? (hipStream_t)stream : ctx->stream);
+  const CookieAge body = {now_ns, d_gen, d_peers};
+  const hipError_t e = launch_each(body, n_peers, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "cookie_age launch");
 }
 

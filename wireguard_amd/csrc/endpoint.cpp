@@ -7,9 +7,9 @@
 //   wgcs_endpoint_dst_jobs_host        Peer.Send up to bind.Send, device/peer.go:201-211
 //   wgcs_endpoint_dst_initiated_host   the same for the initiations of a start call
 //   wgcs_endpoint_dst_responded_host   the same for the responses of an accept call
-// They run the row functions of wgcs_endpoint.h, the code the lanes of
-// endpoint_kernels.hip run, in the passes of the device forms with the rows
-// taken in ascending order.  Plain C++: the host test program
+// They run the bodies of wgcs_endpoint.h, the code the lanes of the device
+// forms run, in the passes of the device forms with the rows taken in
+// ascending order.  Plain C++: the host test program
 // (tests/endpoint_host/endpoint_host.cpp) links this file as it is.
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>  // the library's build compiles every file as HIP: WGCS_HD's qualifiers
@@ -22,22 +22,27 @@ using namespace wgcs;
 
 namespace {
 
-inline bool pow2_or_0(uint32_t n) { return (n & (n - 1)) == 0; }
-
-// claim, then commit: the two launches of a set call
-template <class Finder>
-void set_rows(const Finder& f, uint32_t n, const wgcs_endpoint* ep, wgcs_endpoint* table, uint32_t* claim,
-              wgcs_timers* timers) {
-  for (uint32_t i = 0; i < n; ++i) endpoint_set_claim(i, f.pick(i), claim);
-  for (uint32_t i = 0; i < n; ++i) endpoint_set_commit(i, f.pick(i), ep, table, claim, timers);
+// the two launches of a call, each a loop
+template <class First, class Second>
+void two_passes(const First& first, const Second& second, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) first(i);
+  for (uint32_t i = 0; i < n; ++i) second(i);
 }
 
-// read, then clear: the two launches of a dst call
-template <class Finder>
-void dst_rows(const Finder& f, uint32_t n, wgcs_endpoint* table, wgcs_timers* timers, wgcs_endpoint* dst,
+// claim, then commit: a set call
+template <class Rows>
+void set_rows(const Rows& src, uint32_t n, const wgcs_endpoint* ep, uint32_t n_rows, wgcs_endpoint* table,
+              uint32_t* claim, wgcs_timers* timers) {
+  const EndpointSetClaim<Rows> first = {src, ep, n_rows, claim};
+  two_passes(first, EndpointSetCommit<Rows>{src, ep, n_rows, table, claim, timers}, n);
+}
+
+// read, then clear: a dst call over descriptors
+template <class Rows>
+void dst_rows(const Rows& src, uint32_t n, wgcs_endpoint* table, wgcs_timers* timers, wgcs_endpoint* dst,
               int32_t* dst_v6, int32_t* dst_status) {
-  for (uint32_t j = 0; j < n; ++j) endpoint_dst_read(j, f.row(j), table, timers, dst, dst_v6, dst_status);
-  for (uint32_t j = 0; j < n; ++j) endpoint_dst_clear(f.row(j), table, timers);
+  const EndpointDstRead<Rows> first = {src, table, timers, dst, dst_v6, dst_status};
+  two_passes(first, EndpointDstClear<Rows>{src, table, timers}, n);
 }
 
 }  // namespace
@@ -50,7 +55,8 @@ int wgcs_endpoint_recv_host(const wgcs_src_addr* addr, const int32_t* from, cons
   const uint64_t n = (uint64_t)n_batches * n_msgs;
   if (n == 0) return WGCS_OK;
   if (!endpoint_recv_args_ok(addr, from, size, oob, oob_stride, nn, n, ep, addr_out)) return WGCS_ERR_INVALID_ARG;
-  for (uint32_t q = 0; q < (uint32_t)n; ++q) endpoint_recv(q, n_msgs, addr, from, size, oob, oob_stride, nn, ep, addr_out);
+  const EndpointRecv body = {n_msgs, addr, from, size, oob, oob_stride, nn, ep, addr_out};
+  for (uint32_t q = 0; q < (uint32_t)n; ++q) body(q);
   return WGCS_OK;
 }
 
@@ -62,7 +68,7 @@ int wgcs_endpoint_set_received_host(const wgcs_write_group* groups, uint32_t n_b
   if (n > kMaxRows || !groups || endpoint_misaligned(groups, 7) || (n_ids && !peer_rows) ||
       endpoint_misaligned(peer_rows, 3) || !endpoint_set_tables_ok(ep, n_rows, table, claim, timers, n_peers))
     return WGCS_ERR_INVALID_ARG;
-  set_rows(EndpointReceived{groups, ep, n_rows, peer_rows, n_ids, n_peers}, (uint32_t)n, ep, table, claim, timers);
+  set_rows(GroupRows{groups, peer_rows, n_ids, n_peers}, (uint32_t)n, ep, n_rows, table, claim, timers);
   return WGCS_OK;
 }
 
@@ -73,7 +79,7 @@ int wgcs_endpoint_set_accepted_host(const wgcs_hs_resp* resp, uint32_t n_tickets
   if (n_tickets > kMaxRows || !resp || endpoint_misaligned(resp, 3) ||
       !endpoint_set_tables_ok(ep, n_rows, table, claim, timers, n_peers))
     return WGCS_ERR_INVALID_ARG;
-  set_rows(EndpointAccepted{resp, ep, n_rows, n_peers}, n_tickets, ep, table, claim, timers);
+  set_rows(AcceptedRows{resp, n_peers}, n_tickets, ep, n_rows, table, claim, timers);
   return WGCS_OK;
 }
 
@@ -87,7 +93,7 @@ int wgcs_endpoint_set_finished_host(const uint8_t* arena, const wgcs_aead_pkt* p
       endpoint_misaligned(hs_slots, 3) || endpoint_misaligned(states, 3) ||
       !endpoint_set_tables_ok(ep, n, table, claim, timers, n_peers))
     return WGCS_ERR_INVALID_ARG;
-  set_rows(EndpointFinished{arena, pkts, gate, hs_slots, n_hs_slots, states, n_states, ep, n_peers}, n, ep, table, claim,
+  set_rows(FinishedRows{arena, pkts, gate, hs_slots, n_hs_slots, states, n_states, n_peers}, n, ep, n, table, claim,
            timers);
   return WGCS_OK;
 }
@@ -104,13 +110,9 @@ int wgcs_endpoint_dst_jobs_host(const uint32_t* peer, const int32_t* count, cons
       endpoint_misaligned(lens, 3) || endpoint_misaligned(nbufs, 3) || endpoint_misaligned(peer_rows, 3) ||
       !endpoint_dst_tables_ok(n_jobs, table, timers, n_peers, dst, dst_v6, dst_status, tx_bytes, true))
     return WGCS_ERR_INVALID_ARG;
-  const EndpointJobs f = {peer, count, status, job_key, max_segs, peer_rows, n_ids, n_peers};
-  for (uint32_t j = 0; j < n_jobs; ++j) {
-    const uint32_t row = f.row(j);
-    endpoint_dst_job(j, row, endpoint_dst_read(j, row, table, timers, dst, dst_v6, dst_status), max_segs, lens, nbufs,
-                     tx_bytes);
-  }
-  for (uint32_t j = 0; j < n_jobs; ++j) endpoint_dst_clear(f.row(j), table, timers);
+  const KeptJobRows src = {{peer, count, status, max_segs, peer_rows, n_ids, n_peers}, job_key};
+  two_passes(EndpointDstJobs{{src, table, timers, dst, dst_v6, dst_status}, lens, nbufs, tx_bytes},
+             EndpointDstClear<KeptJobRows>{src, table, timers}, n_jobs);
   return WGCS_OK;
 }
 
@@ -121,7 +123,7 @@ int wgcs_endpoint_dst_initiated_host(const wgcs_hs_start* start, const int32_t* 
   if (!start || !status || endpoint_misaligned(start, 3) || endpoint_misaligned(status, 3) ||
       !endpoint_dst_tables_ok(n, table, timers, n_peers, dst, dst_v6, dst_status, nullptr, false))
     return WGCS_ERR_INVALID_ARG;
-  dst_rows(EndpointInitiated{start, status, n_peers}, n, table, timers, dst, dst_v6, dst_status);
+  dst_rows(InitiatedRows{start, status, n_peers}, n, table, timers, dst, dst_v6, dst_status);
   return WGCS_OK;
 }
 
@@ -132,7 +134,7 @@ int wgcs_endpoint_dst_responded_host(const wgcs_hs_resp* resp, const int32_t* st
   if (!resp || !status || endpoint_misaligned(resp, 3) || endpoint_misaligned(status, 3) ||
       !endpoint_dst_tables_ok(n, table, timers, n_peers, dst, dst_v6, dst_status, nullptr, false))
     return WGCS_ERR_INVALID_ARG;
-  dst_rows(EndpointResponded{resp, status, n_peers}, n, table, timers, dst, dst_v6, dst_status);
+  dst_rows(RespondedRows{resp, status, n_peers}, n, table, timers, dst, dst_v6, dst_status);
   return WGCS_OK;
 }
 

@@ -7,7 +7,8 @@
 //   wgcs_endpoint_dst_jobs_batch        Peer.Send up to bind.Send for send jobs         device/peer.go:201-211
 //   wgcs_endpoint_dst_initiated_batch   ... for initiations
 //   wgcs_endpoint_dst_responded_batch   ... for responses
-// They run in endpoint_kernels.hip; every table is the caller's device memory.
+// They run the bodies of wgcs_endpoint.h through launch_each; every table is the
+// caller's device memory.
 // The argument rules are those of the host forms (endpoint.cpp), shared through
 // wgcs_endpoint.h.
 #include <hip/hip_runtime.h>
@@ -29,6 +30,22 @@ const char kDstArgs[] =
     "NULL, misaligned or overlapping d_table / d_timers / d_dst / d_dst_v6 / d_dst_status / d_tx_bytes, or a count "
     "over its bound";
 
+// claim, then commit: the two launches of a set call
+template <class Rows>
+hipError_t launch_set(const Rows& src, uint32_t n, const wgcs_endpoint* ep, uint32_t n_rows, wgcs_endpoint* table,
+                      uint32_t* claim, wgcs_timers* timers, hipStream_t s) {
+  return launch_each(EndpointSetClaim<Rows>{src, ep, n_rows, claim},
+                     EndpointSetCommit<Rows>{src, ep, n_rows, table, claim, timers}, n, s);
+}
+
+// read, then clear: the two launches of a dst call over descriptors
+template <class Rows>
+hipError_t launch_dst(const Rows& src, uint32_t n, wgcs_endpoint* table, wgcs_timers* timers, wgcs_endpoint* dst,
+                      int32_t* dst_v6, int32_t* dst_status, hipStream_t s) {
+  return launch_each(EndpointDstRead<Rows>{src, table, timers, dst, dst_v6, dst_status},
+                     EndpointDstClear<Rows>{src, table, timers}, n, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -44,8 +61,8 @@ int wgcs_endpoint_recv_batch(wgcs_ctx* ctx, const wgcs_src_addr* d_addr, const i
                    "NULL, misaligned or overlapping argument, oob_stride no multiple of 4, or more than 2^28 slots");
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_endpoint_recv(d_addr, d_from, d_size, d_oob, oob_stride, d_nn, n_msgs, (uint32_t)n, d_ep,
-                                            d_addr_out, stream ? (hipStream_t)stream : ctx->stream);
+  const EndpointRecv body = {n_msgs, d_addr, d_from, d_size, d_oob, oob_stride, d_nn, d_ep, d_addr_out};
+  const hipError_t e = launch_each(body, (uint32_t)n, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "endpoint_recv launch");
 }
 
@@ -63,9 +80,8 @@ int wgcs_endpoint_set_received_batch(wgcs_ctx* ctx, const wgcs_write_group* d_gr
     return set_err(ctx, WGCS_ERR_INVALID_ARG, kSetArgs);
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e =
-      launch_endpoint_set_received(EndpointReceived{d_groups, d_ep, n_rows, d_peer_rows, n_ids, n_peers}, (uint32_t)n,
-                                   d_table, d_claim, d_timers, stream ? (hipStream_t)stream : ctx->stream);
+  const hipError_t e = launch_set(GroupRows{d_groups, d_peer_rows, n_ids, n_peers}, (uint32_t)n, d_ep, n_rows, d_table,
+                                  d_claim, d_timers, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "endpoint_set_received launch");
 }
 
@@ -80,8 +96,8 @@ int wgcs_endpoint_set_accepted_batch(wgcs_ctx* ctx, const wgcs_hs_resp* d_resp, 
     return set_err(ctx, WGCS_ERR_INVALID_ARG, kSetArgs);
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_endpoint_set_accepted(EndpointAccepted{d_resp, d_ep, n_rows, n_peers}, n_tickets, d_table,
-                                                    d_claim, d_timers, stream ? (hipStream_t)stream : ctx->stream);
+  const hipError_t e = launch_set(AcceptedRows{d_resp, n_peers}, n_tickets, d_ep, n_rows, d_table, d_claim, d_timers,
+                                  stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "endpoint_set_accepted launch");
 }
 
@@ -102,9 +118,9 @@ int wgcs_endpoint_set_finished_batch(wgcs_ctx* ctx, const uint8_t* d_arena, cons
     return set_err(ctx, WGCS_ERR_INVALID_ARG, kSetArgs);
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_endpoint_set_finished(
-      EndpointFinished{d_arena, d_pkts, d_gate, d_hs_slots, n_hs_slots, d_states, n_states, d_ep, n_peers}, n, d_table,
-      d_claim, d_timers, stream ? (hipStream_t)stream : ctx->stream);
+  const FinishedRows src = {d_arena, d_pkts, d_gate, d_hs_slots, n_hs_slots, d_states, n_states, n_peers};
+  const hipError_t e =
+      launch_set(src, n, d_ep, n, d_table, d_claim, d_timers, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "endpoint_set_finished launch");
 }
 
@@ -126,9 +142,10 @@ int wgcs_endpoint_dst_jobs_batch(wgcs_ctx* ctx, const uint32_t* d_peer, const in
     return set_err(ctx, WGCS_ERR_INVALID_ARG, kDstArgs);
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_endpoint_dst_jobs(
-      EndpointJobs{d_peer, d_count, d_status, d_job_key, max_segs, d_peer_rows, n_ids, n_peers}, n_jobs, d_lens, d_nbufs,
-      d_table, d_timers, d_dst, d_dst_v6, d_dst_status, d_tx_bytes, stream ? (hipStream_t)stream : ctx->stream);
+  const KeptJobRows src = {{d_peer, d_count, d_status, max_segs, d_peer_rows, n_ids, n_peers}, d_job_key};
+  const hipError_t e = launch_each(
+      EndpointDstJobs{{src, d_table, d_timers, d_dst, d_dst_v6, d_dst_status}, d_lens, d_nbufs, d_tx_bytes},
+      EndpointDstClear<KeptJobRows>{src, d_table, d_timers}, n_jobs, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "endpoint_dst_jobs launch");
 }
 
@@ -143,9 +160,8 @@ int wgcs_endpoint_dst_initiated_batch(wgcs_ctx* ctx, const wgcs_hs_start* d_star
     return set_err(ctx, WGCS_ERR_INVALID_ARG, kDstArgs);
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_endpoint_dst_initiated(EndpointInitiated{d_start, d_status, n_peers}, n, d_table, d_timers,
-                                                     d_dst, d_dst_v6, d_dst_status,
-                                                     stream ? (hipStream_t)stream : ctx->stream);
+  const hipError_t e = launch_dst(InitiatedRows{d_start, d_status, n_peers}, n, d_table, d_timers, d_dst, d_dst_v6,
+                                  d_dst_status, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "endpoint_dst_initiated launch");
 }
 
@@ -160,9 +176,8 @@ int wgcs_endpoint_dst_responded_batch(wgcs_ctx* ctx, const wgcs_hs_resp* d_resp,
     return set_err(ctx, WGCS_ERR_INVALID_ARG, kDstArgs);
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_endpoint_dst_responded(EndpointResponded{d_resp, d_status, n_peers}, n, d_table, d_timers,
-                                                     d_dst, d_dst_v6, d_dst_status,
-                                                     stream ? (hipStream_t)stream : ctx->stream);
+  const hipError_t e = launch_dst(RespondedRows{d_resp, d_status, n_peers}, n, d_table, d_timers, d_dst, d_dst_v6,
+                                  d_dst_status, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "endpoint_dst_responded launch");
 }
 

@@ -6,8 +6,8 @@
 //   wgcs_rekey_received_host     receive.go:80-91
 //   wgcs_rekey_responded_host    send.go:131-133
 //   wgcs_rekey_start_host        send.go:84-100, in the passes of the device form
-// They run the row functions of wgcs_rekey.h, the code the lanes of
-// rekey_kernels.hip run, taken in row order.  Plain C++: the host test program
+// They run the bodies and row functions of wgcs_rekey.h, the code the lanes of
+// the device forms run, taken in row order.  Plain C++: the host test program
 // (tests/rekey_host/rekey_host.cpp) links this file as it is.
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>  // the library's build compiles every file as HIP: WGCS_HD's qualifiers
@@ -42,9 +42,8 @@ int wgcs_rekey_recv_gate_host(wgcs_aead_pkt* pkts, uint32_t n, int64_t now_ns, c
   if (n == 0) return WGCS_OK;
   if (n > kMaxRows || !pkts || (n_keys && !key_peer) || !rows_ok(peer_rows, n_ids, kp, n_peers))
     return WGCS_ERR_INVALID_ARG;
-  for (uint32_t i = 0; i < n; ++i)
-    if (rekey_recv_expired(i, pkts, now_ns, key_peer, n_keys, peer_rows, n_ids, kp, n_peers))
-      pkts[i].key = WGCS_SESSION_EXPIRED;
+  const RekeyRecvGate body = {{pkts, key_peer, n_keys, peer_rows, n_ids, n_peers}, now_ns, kp, pkts};
+  for (uint32_t i = 0; i < n; ++i) body(i);
   return WGCS_OK;
 }
 
@@ -56,9 +55,9 @@ int wgcs_rekey_send_gate_host(const uint32_t* peer, const int32_t* count, const 
   if (!status_out ||
       !jobs_ok(peer, count, status_in, n_jobs, max_segs, peer_rows, n_ids, kp, n_peers, send_nonce, n_keys, rekey))
     return WGCS_ERR_INVALID_ARG;
-  for (uint32_t j = 0; j < n_jobs; ++j)
-    status_out[j] = rekey_send_gate(j, peer, count, status_in, max_segs, now_ns, peer_rows, n_ids, kp, n_peers,
-                                    send_nonce, n_keys, limit, rekey);
+  const RekeySendGate body = {{peer, count, status_in, max_segs, peer_rows, n_ids, n_peers}, now_ns, kp, send_nonce,
+                              n_keys, limit, rekey, status_out};
+  for (uint32_t j = 0; j < n_jobs; ++j) body(j);
   return WGCS_OK;
 }
 
@@ -70,9 +69,9 @@ int wgcs_rekey_sent_host(const uint32_t* peer, const int32_t* count, const int32
   if (!job_key ||
       !jobs_ok(peer, count, status, n_jobs, max_segs, peer_rows, n_ids, kp, n_peers, send_nonce, n_keys, rekey))
     return WGCS_ERR_INVALID_ARG;
-  for (uint32_t j = 0; j < n_jobs; ++j)
-    rekey_sent(j, peer, count, status, job_key, max_segs, now_ns, peer_rows, n_ids, kp, n_peers, send_nonce, n_keys,
-               limit, rekey);
+  const RekeySent body = {{peer, count, status, max_segs, peer_rows, n_ids, n_peers}, job_key, now_ns, kp, send_nonce,
+                          n_keys, limit, rekey};
+  for (uint32_t j = 0; j < n_jobs; ++j) body(j);
   return WGCS_OK;
 }
 
@@ -83,7 +82,8 @@ int wgcs_rekey_received_host(const wgcs_write_group* groups, uint32_t n_batches,
   if (n == 0) return WGCS_OK;
   if (n > kMaxRows || !groups || (n_peers && !rekey) || !rows_ok(peer_rows, n_ids, kp, n_peers))
     return WGCS_ERR_INVALID_ARG;
-  for (uint32_t c = 0; c < (uint32_t)n; ++c) rekey_received(c, groups, now_ns, peer_rows, n_ids, kp, n_peers, rekey);
+  const RekeyReceived body = {{groups, peer_rows, n_ids, n_peers}, now_ns, kp, rekey};
+  for (uint32_t c = 0; c < (uint32_t)n; ++c) body(c);
   return WGCS_OK;
 }
 
@@ -91,7 +91,8 @@ int wgcs_rekey_responded_host(const wgcs_hs_resp* resp, const int32_t* gate, uin
                               wgcs_rekey* rekey, uint32_t n_peers) {
   if (n == 0) return WGCS_OK;
   if (n > kMaxRows || !resp || !gate || (n_peers && !rekey)) return WGCS_ERR_INVALID_ARG;
-  for (uint32_t j = 0; j < n; ++j) rekey_responded(j, resp, gate, now_ns, rekey, n_peers);
+  const RekeyResponded body = {{resp, gate, n_peers}, now_ns, rekey};
+  for (uint32_t j = 0; j < n; ++j) body(j);
   return WGCS_OK;
 }
 

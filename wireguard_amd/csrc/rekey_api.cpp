@@ -5,7 +5,8 @@
 //   wgcs_rekey_received_batch     keepKeyFreshReceiving                             receive.go:80-91
 //   wgcs_rekey_responded_batch    SendHandshakeResponse's lastSentHandshake         send.go:131-133
 //   wgcs_rekey_start_batch        SendHandshakeInitiation up to the message         send.go:84-100
-// They run in rekey_kernels.hip; every table and the start call's scratch are
+// The per-entry calls run their bodies of wgcs_rekey.h through launch_each, start
+// its kernels of rekey_kernels.hip; every table and the start call's scratch are
 // the caller's device memory.  The host functions of the same section are in
 // rekey.cpp.
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 #include "wgcs_ctx.h"
 #include "wgcs_kernels.h"
 #include "wgcs_keyorder.h"
+#include "wgcs_rekey.h"
 
 using namespace wgcs;
 
@@ -58,8 +60,8 @@ int wgcs_rekey_recv_gate_batch(wgcs_ctx* ctx, wgcs_aead_pkt* d_pkts, uint32_t n,
   if (int rc = check_rows(ctx, d_peer_rows, n_ids, d_kp, n_peers)) return rc;
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_rekey_recv_gate(d_pkts, n, now_ns, d_key_peer, n_keys, d_peer_rows, n_ids, d_kp, n_peers,
-                                              stream ? (hipStream_t)stream : ctx->stream);
+  const RekeyRecvGate body = {{d_pkts, d_key_peer, n_keys, d_peer_rows, n_ids, n_peers}, now_ns, d_kp, d_pkts};
+  const hipError_t e = launch_each(body, n, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "rekey_recv_gate launch");
 }
 
@@ -77,9 +79,9 @@ int wgcs_rekey_send_gate_batch(wgcs_ctx* ctx, const uint32_t* d_peer, const int3
     return rc;
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_rekey_send_gate(d_peer, d_count, d_status_in, n_jobs, max_segs, now_ns, d_peer_rows, n_ids,
-                                              d_kp, n_peers, d_send_nonce, n_keys, limit, d_rekey, d_status_out,
-                                              stream ? (hipStream_t)stream : ctx->stream);
+  const RekeySendGate body = {{d_peer, d_count, d_status_in, max_segs, d_peer_rows, n_ids, n_peers}, now_ns, d_kp,
+                              d_send_nonce, n_keys, limit, d_rekey, d_status_out};
+  const hipError_t e = launch_each(body, n_jobs, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "rekey_send_gate launch");
 }
 
@@ -97,9 +99,9 @@ int wgcs_rekey_sent_batch(wgcs_ctx* ctx, const uint32_t* d_peer, const int32_t* 
     return rc;
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_rekey_sent(d_peer, d_count, d_status, d_job_key, n_jobs, max_segs, now_ns, d_peer_rows,
-                                         n_ids, d_kp, n_peers, d_send_nonce, n_keys, limit, d_rekey,
-                                         stream ? (hipStream_t)stream : ctx->stream);
+  const RekeySent body = {{d_peer, d_count, d_status, max_segs, d_peer_rows, n_ids, n_peers}, d_job_key, now_ns, d_kp,
+                          d_send_nonce, n_keys, limit, d_rekey};
+  const hipError_t e = launch_each(body, n_jobs, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "rekey_sent launch");
 }
 
@@ -115,8 +117,8 @@ int wgcs_rekey_received_batch(wgcs_ctx* ctx, const wgcs_write_group* d_groups, u
   if (int rc = check_rows(ctx, d_peer_rows, n_ids, d_kp, n_peers)) return rc;
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_rekey_received(d_groups, (uint32_t)n, now_ns, d_peer_rows, n_ids, d_kp, n_peers, d_rekey,
-                                             stream ? (hipStream_t)stream : ctx->stream);
+  const RekeyReceived body = {{d_groups, d_peer_rows, n_ids, n_peers}, now_ns, d_kp, d_rekey};
+  const hipError_t e = launch_each(body, (uint32_t)n, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "rekey_received launch");
 }
 
@@ -129,8 +131,8 @@ int wgcs_rekey_responded_batch(wgcs_ctx* ctx, const wgcs_hs_resp* d_resp, const 
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "n <= 2^28, 4-byte aligned d_resp / d_gate, 8-byte aligned d_rekey");
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e =
-      launch_rekey_responded(d_resp, d_gate, n, now_ns, d_rekey, n_peers, stream ? (hipStream_t)stream : ctx->stream);
+  const RekeyResponded body = {{d_resp, d_gate, n_peers}, now_ns, d_rekey};
+  const hipError_t e = launch_each(body, n, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "rekey_responded launch");
 }
 

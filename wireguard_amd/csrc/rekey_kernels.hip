@@ -1,11 +1,13 @@
 // rekey_kernels.hip -- keypair expiry, the rekey rules and the start of a
-// handshake on device-resident tables (include/wgcsum.h), the row functions of
-// wgcs_rekey.h one lane at a time:
-//   rekey_recv_gate_kernel     a packet under a keypair past RejectAfterTime      receive.go:162-170
-//   rekey_send_gate_kernel     a job without a usable current keypair             send.go:368-374
-//   rekey_sent_kernel          keepKeyFreshSending behind send-assign             send.go:213-227, :419-420
-//   rekey_received_kernel      keepKeyFreshReceiving over the write groups        receive.go:80-91
-//   rekey_responded_kernel     lastSentHandshake behind respond                   send.go:131-133
+// handshake on device-resident tables (include/wgcsum.h).  The per-entry calls
+// are the bodies of wgcs_rekey.h under the one kernel of wgcs_each.h,
+// instantiated below:
+//   RekeyRecvGate      a packet under a keypair past RejectAfterTime      receive.go:162-170
+//   RekeySendGate      a job without a usable current keypair             send.go:368-374
+//   RekeySent          keepKeyFreshSending behind send-assign             send.go:213-227, :419-420
+//   RekeyReceived      keepKeyFreshReceiving over the write groups        receive.go:80-91
+//   RekeyResponded     lastSentHandshake behind respond                   send.go:131-133
+// and the start call keeps kernels of its own:
 //   start                      SendHandshakeInitiation over the peer rows         send.go:84-100
 //     rekey_start_verdict_kernel   the wish and the timeout of every row
 //     rekey_start_commit_kernel    the descriptor of every candidate that has a ticket, and the tail rows
@@ -20,69 +22,21 @@
 
 #include "../../include/wgcsum.h"
 #include "wgcs_compact.h"
+#include "wgcs_each.h"
 #include "wgcs_kernels.h"
 #include "wgcs_rekey.h"
 
 namespace wgcs {
 
+template hipError_t launch_each(const RekeyRecvGate&, uint32_t, hipStream_t);
+template hipError_t launch_each(const RekeySendGate&, uint32_t, hipStream_t);
+template hipError_t launch_each(const RekeySent&, uint32_t, hipStream_t);
+template hipError_t launch_each(const RekeyReceived&, uint32_t, hipStream_t);
+template hipError_t launch_each(const RekeyResponded&, uint32_t, hipStream_t);
+
 namespace {
 
-constexpr int kThreads = kCompactThreads;  // the one-lane-per-row kernels run the blocks of start's two
-
-__global__ __launch_bounds__(kThreads) void rekey_recv_gate_kernel(wgcs_aead_pkt* pkts, uint32_t n, int64_t now,
-                                                                   const uint32_t* __restrict__ key_peer,
-                                                                   uint32_t n_keys,
-                                                                   const uint32_t* __restrict__ peer_rows,
-                                                                   uint32_t n_ids,
-                                                                   const wgcs_keypairs* __restrict__ kp,
-                                                                   uint32_t n_peers) {
-  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-  if (i >= n) return;
-  if (rekey_recv_expired(i, pkts, now, key_peer, n_keys, peer_rows, n_ids, kp, n_peers))
-    pkts[i].key = WGCS_SESSION_EXPIRED;
-}
-
-// status_out may be status_in: a lane reads its own word and then writes it
-__global__ __launch_bounds__(kThreads) void rekey_send_gate_kernel(
-    const uint32_t* __restrict__ peer, const int32_t* __restrict__ count, const int32_t* status_in, uint32_t n_jobs,
-    uint32_t max_segs, int64_t now, const uint32_t* __restrict__ peer_rows, uint32_t n_ids,
-    const wgcs_keypairs* __restrict__ kp, uint32_t n_peers, const uint64_t* __restrict__ send_nonce, uint32_t n_keys,
-    uint64_t limit, wgcs_rekey* rekey, int32_t* status_out) {
-  const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
-  if (j >= n_jobs) return;
-  status_out[j] = rekey_send_gate(j, peer, count, status_in, max_segs, now, peer_rows, n_ids, kp, n_peers, send_nonce,
-                                  n_keys, limit, rekey);
-}
-
-__global__ __launch_bounds__(kThreads) void rekey_sent_kernel(
-    const uint32_t* __restrict__ peer, const int32_t* __restrict__ count, const int32_t* __restrict__ status,
-    const uint32_t* __restrict__ job_key, uint32_t n_jobs, uint32_t max_segs, int64_t now,
-    const uint32_t* __restrict__ peer_rows, uint32_t n_ids, const wgcs_keypairs* __restrict__ kp, uint32_t n_peers,
-    const uint64_t* __restrict__ send_nonce, uint32_t n_keys, uint64_t limit, wgcs_rekey* rekey) {
-  const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
-  if (j >= n_jobs) return;
-  rekey_sent(j, peer, count, status, job_key, max_segs, now, peer_rows, n_ids, kp, n_peers, send_nonce, n_keys, limit,
-             rekey);
-}
-
-__global__ __launch_bounds__(kThreads) void rekey_received_kernel(const wgcs_write_group* __restrict__ groups,
-                                                                  uint32_t n, int64_t now,
-                                                                  const uint32_t* __restrict__ peer_rows,
-                                                                  uint32_t n_ids,
-                                                                  const wgcs_keypairs* __restrict__ kp,
-                                                                  uint32_t n_peers, wgcs_rekey* rekey) {
-  const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
-  if (c >= n) return;
-  rekey_received(c, groups, now, peer_rows, n_ids, kp, n_peers, rekey);
-}
-
-__global__ __launch_bounds__(kThreads) void rekey_responded_kernel(const wgcs_hs_resp* __restrict__ resp,
-                                                                   const int32_t* __restrict__ gate, uint32_t n,
-                                                                   int64_t now, wgcs_rekey* rekey, uint32_t n_peers) {
-  const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
-  if (j >= n) return;
-  rekey_responded(j, resp, gate, now, rekey, n_peers);
-}
+constexpr int kThreads = kCompactThreads;
 
 // block_cand[b] = the candidates of block b
 __global__ __launch_bounds__(kThreads) void rekey_start_verdict_kernel(int64_t now, wgcs_rekey* rekey, uint32_t n_peers,
@@ -110,49 +64,6 @@ __global__ __launch_bounds__(kThreads) void rekey_start_commit_kernel(
 }
 
 }  // namespace
-
-hipError_t launch_rekey_recv_gate(wgcs_aead_pkt* pkts, uint32_t n, int64_t now, const uint32_t* key_peer,
-                                  uint32_t n_keys, const uint32_t* peer_rows, uint32_t n_ids, const wgcs_keypairs* kp,
-                                  uint32_t n_peers, hipStream_t s) {
-  hipLaunchKernelGGL(rekey_recv_gate_kernel, dim3(compact_blocks(n)), dim3(kThreads), 0, s, pkts, n, now, key_peer,
-                     n_keys, peer_rows, n_ids, kp, n_peers);
-  return hipGetLastError();
-}
-
-hipError_t launch_rekey_send_gate(const uint32_t* peer, const int32_t* count, const int32_t* status_in, uint32_t n_jobs,
-                                  uint32_t max_segs, int64_t now, const uint32_t* peer_rows, uint32_t n_ids,
-                                  const wgcs_keypairs* kp, uint32_t n_peers, const uint64_t* send_nonce,
-                                  uint32_t n_keys, uint64_t limit, wgcs_rekey* rekey, int32_t* status_out,
-                                  hipStream_t s) {
-  hipLaunchKernelGGL(rekey_send_gate_kernel, dim3(compact_blocks(n_jobs)), dim3(kThreads), 0, s, peer, count, status_in,
-                     n_jobs, max_segs, now, peer_rows, n_ids, kp, n_peers, send_nonce, n_keys, limit, rekey,
-                     status_out);
-  return hipGetLastError();
-}
-
-hipError_t launch_rekey_sent(const uint32_t* peer, const int32_t* count, const int32_t* status, const uint32_t* job_key,
-                             uint32_t n_jobs, uint32_t max_segs, int64_t now, const uint32_t* peer_rows,
-                             uint32_t n_ids, const wgcs_keypairs* kp, uint32_t n_peers, const uint64_t* send_nonce,
-                             uint32_t n_keys, uint64_t limit, wgcs_rekey* rekey, hipStream_t s) {
-  hipLaunchKernelGGL(rekey_sent_kernel, dim3(compact_blocks(n_jobs)), dim3(kThreads), 0, s, peer, count, status,
-                     job_key, n_jobs, max_segs, now, peer_rows, n_ids, kp, n_peers, send_nonce, n_keys, limit, rekey);
-  return hipGetLastError();
-}
-
-hipError_t launch_rekey_received(const wgcs_write_group* groups, uint32_t n, int64_t now, const uint32_t* peer_rows,
-                                 uint32_t n_ids, const wgcs_keypairs* kp, uint32_t n_peers, wgcs_rekey* rekey,
-                                 hipStream_t s) {
-  hipLaunchKernelGGL(rekey_received_kernel, dim3(compact_blocks(n)), dim3(kThreads), 0, s, groups, n, now, peer_rows,
-                     n_ids, kp, n_peers, rekey);
-  return hipGetLastError();
-}
-
-hipError_t launch_rekey_responded(const wgcs_hs_resp* resp, const int32_t* gate, uint32_t n, int64_t now,
-                                  wgcs_rekey* rekey, uint32_t n_peers, hipStream_t s) {
-  hipLaunchKernelGGL(rekey_responded_kernel, dim3(compact_blocks(n)), dim3(kThreads), 0, s, resp, gate, n, now, rekey,
-                     n_peers);
-  return hipGetLastError();
-}
 
 hipError_t launch_rekey_start(int64_t now, wgcs_rekey* rekey, const wgcs_hs_peer* hs_peers, uint32_t n_peers,
                               const wgcs_hs_start* tickets, uint32_t n_tickets, wgcs_hs_start* start,

@@ -8,8 +8,8 @@
 //   wgcs_timers_finished_host     receive.go:339-348
 //   wgcs_timers_rotated_host      receive.go:422-427
 //   wgcs_timers_expire_host       device/timers.go:73-144, in the passes of the device form
-// They run the row functions of wgcs_timers.h, the code the lanes of
-// timers_kernels.hip run, taken in row order.  Plain C++: the host test program
+// They run the bodies and row functions of wgcs_timers.h, the code the lanes of
+// the device forms run, taken in row order.  Plain C++: the host test program
 // (tests/timers_host/timers_host.cpp) links this file as it is.
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>  // the library's build compiles every file as HIP: WGCS_HD's qualifiers
@@ -22,8 +22,6 @@
 using namespace wgcs;
 
 namespace {
-
-inline bool pow2_or_0(uint32_t n) { return (n & (n - 1)) == 0; }
 
 // a table of n_peers rows and the id -> row map in front of it
 inline bool rows_ok(const uint32_t* peer_rows, uint32_t n_ids, const void* table, uint32_t n_peers) {
@@ -44,9 +42,9 @@ int wgcs_timers_sent_host(const int32_t* sizes, const uint32_t* peer, const int3
   if (!sizes || !peer || !count || !status || !job_key || max_segs == 0 || (uint64_t)n_jobs * max_segs > kMaxRows ||
       !rows_ok(peer_rows, n_ids, timers, n_peers))
     return WGCS_ERR_INVALID_ARG;
-  for (uint32_t j = 0; j < n_jobs; ++j)
-    timers_sent(j, sizes, peer, count, status, job_key, max_segs, now_ns, jitter_seed, peer_rows, n_ids, timers,
-                n_peers);
+  const TimersSent body = {{{peer, count, status, max_segs, peer_rows, n_ids, n_peers}, job_key}, sizes, now_ns,
+                           jitter_seed, timers};
+  for (uint32_t j = 0; j < n_jobs; ++j) body(j);
   return WGCS_OK;
 }
 
@@ -56,7 +54,8 @@ int wgcs_timers_received_host(const wgcs_write_group* groups, uint32_t n_batches
   const uint64_t n = (uint64_t)n_batches * calls_per_batch;
   if (n == 0) return WGCS_OK;
   if (n > kMaxRows || !groups || !rows_ok(peer_rows, n_ids, timers, n_peers)) return WGCS_ERR_INVALID_ARG;
-  for (uint32_t c = 0; c < (uint32_t)n; ++c) timers_received(c, groups, now_ns, peer_rows, n_ids, timers, n_peers);
+  const TimersReceived body = {{groups, peer_rows, n_ids, n_peers}, now_ns, timers};
+  for (uint32_t c = 0; c < (uint32_t)n; ++c) body(c);
   return WGCS_OK;
 }
 
@@ -68,9 +67,10 @@ int wgcs_timers_initiated_host(const uint32_t* reasons, const uint32_t* start_pe
       (n_tickets && (!start_peer || !init_status)))
     return WGCS_ERR_INVALID_ARG;
   // the launches of the device form, each a loop: the peer rows, then the tickets
-  for (uint32_t r = 0; r < n_peers; ++r) timers_initiated_fresh(r, reasons, timers);
-  for (uint32_t k = 0; k < n_tickets; ++k)
-    timers_initiated(k, start_peer, init_status, now_ns, jitter_seed, timers, n_peers);
+  const TimersFresh fresh = {reasons, timers};
+  const TimersInitiated body = {{start_peer, init_status, n_peers}, now_ns, jitter_seed, timers};
+  for (uint32_t r = 0; r < n_peers; ++r) fresh(r);
+  for (uint32_t k = 0; k < n_tickets; ++k) body(k);
   return WGCS_OK;
 }
 
@@ -78,7 +78,8 @@ int wgcs_timers_responded_host(const wgcs_hs_resp* resp, const int32_t* gate, ui
                                wgcs_timers* timers, uint32_t n_peers) {
   if (n == 0) return WGCS_OK;
   if (n > kMaxRows || n_peers > kMaxPeers || !resp || !gate || (n_peers && !timers)) return WGCS_ERR_INVALID_ARG;
-  for (uint32_t j = 0; j < n; ++j) timers_responded(j, resp, gate, now_ns, timers, n_peers);
+  const TimersResponded body = {{resp, gate, n_peers}, now_ns, timers};
+  for (uint32_t j = 0; j < n; ++j) body(j);
   return WGCS_OK;
 }
 
@@ -90,9 +91,9 @@ int wgcs_timers_finished_host(const uint8_t* arena, const wgcs_aead_pkt* pkts, c
   if (n > kMaxPeers || n_peers > kMaxPeers || !arena || !pkts || !gate || !begun || (n_hs_slots && !hs_slots) ||
       !pow2_or_0(n_hs_slots) || (n_states && !states) || (n_peers && (!timers || !rekey)))
     return WGCS_ERR_INVALID_ARG;
-  for (uint32_t q = 0; q < n; ++q)
-    timers_finished(q, arena, pkts, gate, begun, now_ns, hs_slots, n_hs_slots, states, n_states, timers, rekey,
-                    n_peers);
+  const TimersFinished body = {{arena, pkts, gate, hs_slots, n_hs_slots, states, n_states, n_peers}, begun, now_ns,
+                               timers, rekey};
+  for (uint32_t q = 0; q < n; ++q) body(q);
   return WGCS_OK;
 }
 
@@ -103,8 +104,8 @@ int wgcs_timers_rotated_host(const wgcs_aead_pkt* pkts, const uint32_t* rotated,
   if (n > kMaxRows || !pkts || !rotated || (n_keys && !key_peer) || (n_peers && !rekey) ||
       !rows_ok(peer_rows, n_ids, timers, n_peers))
     return WGCS_ERR_INVALID_ARG;
-  for (uint32_t i = 0; i < n; ++i)
-    timers_rotated(i, pkts, rotated, now_ns, key_peer, n_keys, peer_rows, n_ids, timers, rekey, n_peers);
+  const TimersRotated body = {{pkts, key_peer, n_keys, peer_rows, n_ids, n_peers}, rotated, now_ns, timers, rekey};
+  for (uint32_t i = 0; i < n; ++i) body(i);
   return WGCS_OK;
 }
 

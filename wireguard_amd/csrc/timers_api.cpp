@@ -6,8 +6,9 @@
 //   wgcs_timers_finished_batch     behind begin-initiator              receive.go:339-348
 //   wgcs_timers_rotated_batch      behind keypairs-received            receive.go:422-427
 //   wgcs_timers_expire_batch       the expiry of the five timers       device/timers.go:73-144
-// They run in timers_kernels.hip; every table and the expire call's scratch are
-// the caller's device memory.  The host functions of the same section are in
+// The event calls run their bodies of wgcs_timers.h through launch_each, expire
+// its kernels of timers_kernels.hip; every table and the expire call's scratch
+// are the caller's device memory.  The host functions of the same section are in
 // timers.cpp.
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,7 @@
 #include "wgcs_ctx.h"
 #include "wgcs_kernels.h"
 #include "wgcs_keyorder.h"
+#include "wgcs_timers.h"
 
 using namespace wgcs;
 
@@ -52,9 +54,9 @@ int wgcs_timers_sent_batch(wgcs_ctx* ctx, const int32_t* d_sizes, const uint32_t
   if (int rc = check_rows(ctx, d_peer_rows, n_ids, d_timers, n_peers)) return rc;
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_timers_sent(d_sizes, d_peer, d_count, d_status, d_job_key, n_jobs, max_segs, now_ns,
-                                          jitter_seed, d_peer_rows, n_ids, d_timers, n_peers,
-                                          stream ? (hipStream_t)stream : ctx->stream);
+  const TimersSent body = {{{d_peer, d_count, d_status, max_segs, d_peer_rows, n_ids, n_peers}, d_job_key},
+                           d_sizes, now_ns, jitter_seed, d_timers};
+  const hipError_t e = launch_each(body, n_jobs, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "timers_sent launch");
 }
 
@@ -70,8 +72,8 @@ int wgcs_timers_received_batch(wgcs_ctx* ctx, const wgcs_write_group* d_groups, 
   if (int rc = check_rows(ctx, d_peer_rows, n_ids, d_timers, n_peers)) return rc;
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_timers_received(d_groups, (uint32_t)n, now_ns, d_peer_rows, n_ids, d_timers, n_peers,
-                                              stream ? (hipStream_t)stream : ctx->stream);
+  const TimersReceived body = {{d_groups, d_peer_rows, n_ids, n_peers}, now_ns, d_timers};
+  const hipError_t e = launch_each(body, (uint32_t)n, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "timers_received launch");
 }
 
@@ -89,8 +91,12 @@ int wgcs_timers_initiated_batch(wgcs_ctx* ctx, const uint32_t* d_reasons, const 
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "8-byte aligned d_timers, 4-byte aligned rows");
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_timers_initiated(d_reasons, d_start_peer, d_init_status, n_tickets, now_ns, jitter_seed,
-                                               d_timers, n_peers, stream ? (hipStream_t)stream : ctx->stream);
+  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  // the peer rows, then the tickets
+  hipError_t e = launch_each(TimersFresh{d_reasons, d_timers}, n_peers, s);
+  if (e == hipSuccess && n_tickets)
+    e = launch_each(TimersInitiated{{d_start_peer, d_init_status, n_peers}, now_ns, jitter_seed, d_timers}, n_tickets,
+                    s);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "timers_initiated launch");
 }
 
@@ -104,8 +110,8 @@ int wgcs_timers_responded_batch(wgcs_ctx* ctx, const wgcs_hs_resp* d_resp, const
                    "n <= 2^28, n_peers <= 2^24, 4-byte aligned d_resp / d_gate, 8-byte aligned d_timers");
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e =
-      launch_timers_responded(d_resp, d_gate, n, now_ns, d_timers, n_peers, stream ? (hipStream_t)stream : ctx->stream);
+  const TimersResponded body = {{d_resp, d_gate, n_peers}, now_ns, d_timers};
+  const hipError_t e = launch_each(body, n, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "timers_responded launch");
 }
 
@@ -126,9 +132,9 @@ int wgcs_timers_finished_batch(wgcs_ctx* ctx, const uint8_t* d_arena, const wgcs
     return set_err(ctx, WGCS_ERR_INVALID_ARG, "8-byte aligned d_pkts / d_timers / d_rekey, 4-byte aligned rows");
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e =
-      launch_timers_finished(d_arena, d_pkts, d_gate, d_begun, n, now_ns, d_hs_slots, n_hs_slots, d_states, n_states,
-                             d_timers, d_rekey, n_peers, stream ? (hipStream_t)stream : ctx->stream);
+  const TimersFinished body = {{d_arena, d_pkts, d_gate, d_hs_slots, n_hs_slots, d_states, n_states, n_peers},
+                               d_begun, now_ns, d_timers, d_rekey};
+  const hipError_t e = launch_each(body, n, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "timers_finished launch");
 }
 
@@ -146,8 +152,9 @@ int wgcs_timers_rotated_batch(wgcs_ctx* ctx, const wgcs_aead_pkt* d_pkts, const 
   if (int rc = check_rows(ctx, d_peer_rows, n_ids, d_timers, n_peers)) return rc;
   std::lock_guard<std::mutex> g(ctx->mu);
   hipSetDevice(ctx->device);
-  const hipError_t e = launch_timers_rotated(d_pkts, d_rotated, n, now_ns, d_key_peer, n_keys, d_peer_rows, n_ids,
-                                             d_timers, d_rekey, n_peers, stream ? (hipStream_t)stream : ctx->stream);
+  const TimersRotated body = {{d_pkts, d_key_peer, n_keys, d_peer_rows, n_ids, n_peers}, d_rotated, now_ns, d_timers,
+                              d_rekey};
+  const hipError_t e = launch_each(body, n, stream ? (hipStream_t)stream : ctx->stream);
   return e == hipSuccess ? WGCS_OK : hip_fail(ctx, e, "timers_rotated launch");
 }
 

@@ -1,13 +1,15 @@
 // timers_kernels.hip -- the peer timers on device-resident tables
-// (include/wgcsum.h), the row functions of wgcs_timers.h one lane at a time:
-//   timers_sent_kernel         behind send-assign                      send.go:498-510
-//   timers_received_kernel     over the write groups                   receive.go:486-494
-//   timers_fresh_kernel        !isRetry over the peer rows             send.go:85-87
-//   timers_initiated_kernel    over the start call's tickets           send.go:117-126
-//   timers_responded_kernel    behind respond                          receive.go:311-312, send.go:158-160
-//   timers_finished_kernel     behind begin-initiator                  receive.go:339-348
-//   timers_rotated_kernel      behind keypairs-received                receive.go:422-427
-//   expire                     the five expiry bodies over the peer rows   timers.go:73-144
+// (include/wgcsum.h).  The event calls are the bodies of wgcs_timers.h under
+// the one kernel of wgcs_each.h, instantiated below:
+//   TimersSent         behind send-assign                      send.go:498-510
+//   TimersReceived     over the write groups                   receive.go:486-494
+//   TimersFresh        !isRetry over the peer rows             send.go:85-87
+//   TimersInitiated    over the start call's tickets           send.go:117-126
+//   TimersResponded    behind respond                          receive.go:311-312, send.go:158-160
+//   TimersFinished     behind begin-initiator                  receive.go:339-348
+//   TimersRotated      behind keypairs-received                receive.go:422-427
+// and the expiry keeps kernels of its own:
+//   expire             the five expiry bodies over the peer rows   timers.go:73-144
 //     timers_expire_verdict_kernel   every due timer of a row
 //     timers_expire_commit_kernel    the keepalive job of every owing row that has room, and the tail jobs
 //   The rows that owe a keepalive are compacted into the jobs by the scheme of wgcs_compact.h,
@@ -21,78 +23,23 @@
 
 #include "../../include/wgcsum.h"
 #include "wgcs_compact.h"
+#include "wgcs_each.h"
 #include "wgcs_kernels.h"
 #include "wgcs_timers.h"
 
 namespace wgcs {
 
+template hipError_t launch_each(const TimersSent&, uint32_t, hipStream_t);
+template hipError_t launch_each(const TimersReceived&, uint32_t, hipStream_t);
+template hipError_t launch_each(const TimersFresh&, uint32_t, hipStream_t);
+template hipError_t launch_each(const TimersInitiated&, uint32_t, hipStream_t);
+template hipError_t launch_each(const TimersResponded&, uint32_t, hipStream_t);
+template hipError_t launch_each(const TimersFinished&, uint32_t, hipStream_t);
+template hipError_t launch_each(const TimersRotated&, uint32_t, hipStream_t);
+
 namespace {
 
-constexpr int kThreads = kCompactThreads;  // the one-lane-per-row kernels run the blocks of expire's two
-
-__global__ __launch_bounds__(kThreads) void timers_sent_kernel(
-    const int32_t* __restrict__ sizes, const uint32_t* __restrict__ peer, const int32_t* __restrict__ count,
-    const int32_t* __restrict__ status, const uint32_t* __restrict__ job_key, uint32_t n_jobs, uint32_t max_segs,
-    int64_t now, uint32_t seed, const uint32_t* __restrict__ peer_rows, uint32_t n_ids, wgcs_timers* timers,
-    uint32_t n_peers) {
-  const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
-  if (j >= n_jobs) return;
-  timers_sent(j, sizes, peer, count, status, job_key, max_segs, now, seed, peer_rows, n_ids, timers, n_peers);
-}
-
-__global__ __launch_bounds__(kThreads) void timers_received_kernel(const wgcs_write_group* __restrict__ groups,
-                                                                   uint32_t n, int64_t now,
-                                                                   const uint32_t* __restrict__ peer_rows,
-                                                                   uint32_t n_ids, wgcs_timers* timers,
-                                                                   uint32_t n_peers) {
-  const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
-  if (c >= n) return;
-  timers_received(c, groups, now, peer_rows, n_ids, timers, n_peers);
-}
-
-__global__ __launch_bounds__(kThreads) void timers_fresh_kernel(const uint32_t* __restrict__ reasons,
-                                                                wgcs_timers* timers, uint32_t n_peers) {
-  const uint32_t r = blockIdx.x * kThreads + threadIdx.x;
-  if (r >= n_peers) return;
-  timers_initiated_fresh(r, reasons, timers);
-}
-
-__global__ __launch_bounds__(kThreads) void timers_initiated_kernel(const uint32_t* __restrict__ start_peer,
-                                                                    const int32_t* __restrict__ init_status,
-                                                                    uint32_t n_tickets, int64_t now, uint32_t seed,
-                                                                    wgcs_timers* timers, uint32_t n_peers) {
-  const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
-  if (k >= n_tickets) return;
-  timers_initiated(k, start_peer, init_status, now, seed, timers, n_peers);
-}
-
-__global__ __launch_bounds__(kThreads) void timers_responded_kernel(const wgcs_hs_resp* __restrict__ resp,
-                                                                    const int32_t* __restrict__ gate, uint32_t n,
-                                                                    int64_t now, wgcs_timers* timers,
-                                                                    uint32_t n_peers) {
-  const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
-  if (j >= n) return;
-  timers_responded(j, resp, gate, now, timers, n_peers);
-}
-
-__global__ __launch_bounds__(kThreads) void timers_finished_kernel(
-    const uint8_t* __restrict__ arena, const wgcs_aead_pkt* __restrict__ pkts, const int32_t* __restrict__ gate,
-    const int32_t* __restrict__ begun, uint32_t n, int64_t now, const wgcs_session_slot* __restrict__ hs_slots,
-    uint32_t n_hs_slots, const wgcs_hs_state* __restrict__ states, uint32_t n_states, wgcs_timers* timers,
-    wgcs_rekey* rekey, uint32_t n_peers) {
-  const uint32_t q = blockIdx.x * kThreads + threadIdx.x;
-  if (q >= n) return;
-  timers_finished(q, arena, pkts, gate, begun, now, hs_slots, n_hs_slots, states, n_states, timers, rekey, n_peers);
-}
-
-__global__ __launch_bounds__(kThreads) void timers_rotated_kernel(
-    const wgcs_aead_pkt* __restrict__ pkts, const uint32_t* __restrict__ rotated, uint32_t n, int64_t now,
-    const uint32_t* __restrict__ key_peer, uint32_t n_keys, const uint32_t* __restrict__ peer_rows, uint32_t n_ids,
-    wgcs_timers* timers, wgcs_rekey* rekey, uint32_t n_peers) {
-  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-  if (i >= n) return;
-  timers_rotated(i, pkts, rotated, now, key_peer, n_keys, peer_rows, n_ids, timers, rekey, n_peers);
-}
+constexpr int kThreads = kCompactThreads;
 
 // block_owe[b] = the rows of block b that owe a keepalive job
 __global__ __launch_bounds__(kThreads) void timers_expire_verdict_kernel(
@@ -121,61 +68,6 @@ __global__ __launch_bounds__(kThreads) void timers_expire_commit_kernel(
 }
 
 }  // namespace
-
-hipError_t launch_timers_sent(const int32_t* sizes, const uint32_t* peer, const int32_t* count, const int32_t* status,
-                              const uint32_t* job_key, uint32_t n_jobs, uint32_t max_segs, int64_t now, uint32_t seed,
-                              const uint32_t* peer_rows, uint32_t n_ids, wgcs_timers* timers, uint32_t n_peers,
-                              hipStream_t s) {
-  hipLaunchKernelGGL(timers_sent_kernel, dim3(compact_blocks(n_jobs)), dim3(kThreads), 0, s, sizes, peer, count, status,
-                     job_key, n_jobs, max_segs, now, seed, peer_rows, n_ids, timers, n_peers);
-  return hipGetLastError();
-}
-
-hipError_t launch_timers_received(const wgcs_write_group* groups, uint32_t n, int64_t now, const uint32_t* peer_rows,
-                                  uint32_t n_ids, wgcs_timers* timers, uint32_t n_peers, hipStream_t s) {
-  hipLaunchKernelGGL(timers_received_kernel, dim3(compact_blocks(n)), dim3(kThreads), 0, s, groups, n, now, peer_rows,
-                     n_ids, timers, n_peers);
-  return hipGetLastError();
-}
-
-hipError_t launch_timers_initiated(const uint32_t* reasons, const uint32_t* start_peer, const int32_t* init_status,
-                                   uint32_t n_tickets, int64_t now, uint32_t seed, wgcs_timers* timers,
-                                   uint32_t n_peers, hipStream_t s) {
-  hipError_t e;
-  if (n_peers) {
-    hipLaunchKernelGGL(timers_fresh_kernel, dim3(compact_blocks(n_peers)), dim3(kThreads), 0, s, reasons, timers,
-                       n_peers);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if (n_tickets == 0 || n_peers == 0) return hipSuccess;
-  hipLaunchKernelGGL(timers_initiated_kernel, dim3(compact_blocks(n_tickets)), dim3(kThreads), 0, s, start_peer,
-                     init_status, n_tickets, now, seed, timers, n_peers);
-  return hipGetLastError();
-}
-
-hipError_t launch_timers_responded(const wgcs_hs_resp* resp, const int32_t* gate, uint32_t n, int64_t now,
-                                   wgcs_timers* timers, uint32_t n_peers, hipStream_t s) {
-  hipLaunchKernelGGL(timers_responded_kernel, dim3(compact_blocks(n)), dim3(kThreads), 0, s, resp, gate, n, now, timers,
-                     n_peers);
-  return hipGetLastError();
-}
-
-hipError_t launch_timers_finished(const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* gate,
-                                  const int32_t* begun, uint32_t n, int64_t now, const wgcs_session_slot* hs_slots,
-                                  uint32_t n_hs_slots, const wgcs_hs_state* states, uint32_t n_states,
-                                  wgcs_timers* timers, wgcs_rekey* rekey, uint32_t n_peers, hipStream_t s) {
-  hipLaunchKernelGGL(timers_finished_kernel, dim3(compact_blocks(n)), dim3(kThreads), 0, s, arena, pkts, gate, begun, n,
-                     now, hs_slots, n_hs_slots, states, n_states, timers, rekey, n_peers);
-  return hipGetLastError();
-}
-
-hipError_t launch_timers_rotated(const wgcs_aead_pkt* pkts, const uint32_t* rotated, uint32_t n, int64_t now,
-                                 const uint32_t* key_peer, uint32_t n_keys, const uint32_t* peer_rows, uint32_t n_ids,
-                                 wgcs_timers* timers, wgcs_rekey* rekey, uint32_t n_peers, hipStream_t s) {
-  hipLaunchKernelGGL(timers_rotated_kernel, dim3(compact_blocks(n)), dim3(kThreads), 0, s, pkts, rotated, n, now,
-                     key_peer, n_keys, peer_rows, n_ids, timers, rekey, n_peers);
-  return hipGetLastError();
-}
 
 hipError_t launch_timers_expire(int64_t now, wgcs_timers* timers, wgcs_rekey* rekey, const wgcs_peer_key* table,
                                 uint32_t n_peers, const uint32_t* staged, wgcs_keypairs* kp, wgcs_session_slot* slots,

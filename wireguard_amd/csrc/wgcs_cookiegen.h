@@ -4,9 +4,9 @@
 //   consume    the cookie-reply case of RoutineHandshake with ConsumeReply
 //                                            receive.go:246-269, cookie.go:319-339
 //   age        the CookieRefreshTime rule    cookie.go:306
-// cookiegen_kernels.hip runs them one lane per row, cookiegen.cpp in row order,
-// and the stand-alone sanitizer program of tests/cookiegen_host/ includes this
-// one text.
+// Each pass is a body that wgcs_each.h runs one lane per row and cookiegen.cpp
+// in row order, the recording calls over the sources of wgcs_events.h; the
+// stand-alone sanitizer program of tests/cookiegen_host/ includes this one text.
 //
 // Several rows of a call may belong to one peer.  The reference takes them in
 // turn, so the last one's 16 bytes stand; here every such row raises the peer's
@@ -27,7 +27,7 @@
 
 #pragma push_macro("WGCS_HD")  // wgcs_route_walk.h defines its own, plain inline: keep the forced one of wgcs_poly1305.h
 #undef WGCS_HD
-#include "wgcs_route_walk.h"  // session_get
+#include "wgcs_events.h"  // and wgcs_route_walk.h's session_get
 #pragma pop_macro("WGCS_HD")
 
 namespace wgcs {
@@ -49,60 +49,50 @@ WGCS_HD uint32_t* cookiegen_words(wgcs_cookie_gen* g) { return (uint32_t*)g; }
 WGCS_HD const uint32_t* cookiegen_words(const wgcs_cookie_gen* g) { return (const uint32_t*)g; }
 WGCS_HD uint32_t* cookiegen_words(wgcs_hs_peer* p) { return (uint32_t*)p; }
 
-// *claim = max(*claim, ticket).  On the device a plain look comes first, as in
-// keypairs_received_claim: the claim only rises within a pass, so a stale value
-// costs an atomic and never a claim.
-WGCS_HD void cookiegen_claim(uint32_t* claim, uint32_t ticket) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  if (ticket > __hip_atomic_load(claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(claim, ticket);
-#else
-  if (ticket > *claim) *claim = ticket;
-#endif
-}
-
 // ---- lastMAC1 behind initiate and respond, cookie.go:301-302, in two passes ----
 
-// the row of d_gen that descriptor j records into, or WGCS_PEER_NONE for one that takes no part
-WGCS_HD uint32_t cookiegen_initiated_row(uint32_t j, const wgcs_hs_start* start, const int32_t* status,
-                                         uint32_t n_peers) {
-  if (status[j] != WGCS_HS_INITIATED) return WGCS_PEER_NONE;
-  const uint32_t row = start[j].peer_row;
-  return row < n_peers ? row : WGCS_PEER_NONE;
-}
-
-WGCS_HD uint32_t cookiegen_responded_row(uint32_t j, const wgcs_hs_resp* resp, const int32_t* status,
-                                         uint32_t n_peers) {
-  if (status[j] != WGCS_HS_RESPONDED) return WGCS_PEER_NONE;
-  const uint32_t row = resp[j].peer_row;
-  return row < n_peers ? row : WGCS_PEER_NONE;
-}
-
-// the MAC1 of message j of a 4-byte aligned d_msgs, as words
-WGCS_HD const uint32_t* cookiegen_initiated_mac1(uint32_t j, const uint8_t* msgs) {
+// the MAC1 of message j of a 4-byte aligned d_msgs, as words, for the call's source
+WGCS_HD const uint32_t* cookiegen_mac1(const InitiatedRows&, uint32_t j, const uint8_t* msgs) {
   return (const uint32_t*)(msgs + (uint64_t)kInitiationPitch * j + kInitiationMac1);
 }
 
-WGCS_HD const uint32_t* cookiegen_responded_mac1(uint32_t j, const uint8_t* msgs) {
+WGCS_HD const uint32_t* cookiegen_mac1(const RespondedRows&, uint32_t j, const uint8_t* msgs) {
   return (const uint32_t*)(msgs + (uint64_t)kResponsePitch * j + kResponseMac1);
 }
 
 // the first pass: descriptor j claims its peer's row
-WGCS_HD void cookiegen_sent_claim(uint32_t j, uint32_t row, wgcs_cookie_gen* gen) {
-  if (row != WGCS_PEER_NONE) cookiegen_claim(cookiegen_words(gen + row) + kGenClaim, j + 1);
-}
+template <class Rows>
+struct CookieSentClaim {
+  Rows src;
+  wgcs_cookie_gen* gen;
+  WGCS_HD void operator()(uint32_t j) const {
+    const uint32_t row = src.row(j);
+    if (row != WGCS_PEER_NONE) claim_max(cookiegen_words(gen + row) + kGenClaim, j + 1);
+  }
+};
 
 // the second pass: the holder of the claim, the highest j of its peer, leaves its MAC1
-WGCS_HD void cookiegen_sent_commit(uint32_t j, uint32_t row, const uint32_t* mac1, wgcs_cookie_gen* gen) {
-  if (row == WGCS_PEER_NONE) return;
-  uint32_t* const g = cookiegen_words(gen + row);
-  if (g[kGenClaim] != j + 1) return;  // a higher descriptor's, or 0 once that one has committed: never j + 1
+template <class Rows>
+struct CookieSentCommit {
+  Rows src;
+  const uint8_t* msgs;
+  wgcs_cookie_gen* gen;
+  WGCS_HD void operator()(uint32_t j) const {
+    const uint32_t row = src.row(j);
+    if (row == WGCS_PEER_NONE) return;
+    uint32_t* const g = cookiegen_words(gen + row);
+    if (g[kGenClaim] != j + 1) return;  // a higher descriptor's, or 0 once that one has committed: never j + 1
+    const uint32_t* const mac1 = cookiegen_mac1(src, j, msgs);
+    // read whole, then stored: nothing tells the compiler that msgs and gen are apart
+    const uint32_t m[4] = {mac1[0], mac1[1], mac1[2], mac1[3]};
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-  for (uint32_t i = 0; i < 4; ++i) g[kGenMac1 + i] = mac1[i];
-  g[kGenFlags] |= WGCS_COOKIE_GEN_HAS_MAC1;
-  g[kGenClaim] = 0;
-}
+    for (uint32_t i = 0; i < 4; ++i) g[kGenMac1 + i] = m[i];
+    g[kGenFlags] |= WGCS_COOKIE_GEN_HAS_MAC1;
+    g[kGenClaim] = 0;
+  }
+};
 
 // ---- cookie replies, receive.go:246-269 and cookie.go:319-339, in two passes ----
 
@@ -161,76 +151,98 @@ WGCS_HD uint32_t cookiegen_peer_row(uint32_t receiver, const CookieGenTables& t)
 
 // The first pass, row q: its verdict.  A reply that opens leaves its cookie in work[4q, 4q + 4)
 // and claims its peer's row; nothing else is written.
-WGCS_HD int32_t cookiegen_open(uint32_t q, const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* types,
-                               const CookieGenTables& t, wgcs_cookie_gen* gen, uint32_t* work) {
-  if (types[q] != (int32_t)kCookieReplyType) return WGCS_HS_NONE;
-  if (pkts[q].len != kCookieReplySize) return WGCS_ERR_INVALID_ARG;
-  uint32_t m[16];
-  cookiegen_load_reply(arena + pkts[q].off, m);
-  if (m[0] != kCookieReplyType) return WGCS_ERR_INVALID_ARG;  // unmarshal, receive.go:249-253
-  const uint32_t row = cookiegen_peer_row(m[1], t);
-  if (row == WGCS_PEER_NONE) return WGCS_ERR_NO_PEER;  // :255-259
-  uint32_t* const g = cookiegen_words(gen + row);
-  if (!(g[kGenFlags] & WGCS_COOKIE_GEN_HAS_MAC1)) return WGCS_ERR_NO_HANDSHAKE;  // cookie.go:323-325
-  uint32_t key[8], ad[4], pt[4];
+struct CookieOpen {
+  const uint8_t* arena;
+  const wgcs_aead_pkt* pkts;
+  const int32_t* types;
+  CookieGenTables t;
+  wgcs_cookie_gen* gen;
+  uint32_t* work;
+  int32_t* verdict;
+  WGCS_HD void operator()(uint32_t q) const { verdict[q] = open(q); }
+  WGCS_HD int32_t open(uint32_t q) const {
+    if (types[q] != (int32_t)kCookieReplyType) return WGCS_HS_NONE;
+    if (pkts[q].len != kCookieReplySize) return WGCS_ERR_INVALID_ARG;
+    uint32_t m[16];
+    cookiegen_load_reply(arena + pkts[q].off, m);
+    if (m[0] != kCookieReplyType) return WGCS_ERR_INVALID_ARG;  // unmarshal, receive.go:249-253
+    const uint32_t row = cookiegen_peer_row(m[1], t);
+    if (row == WGCS_PEER_NONE) return WGCS_ERR_NO_PEER;  // :255-259
+    uint32_t* const g = cookiegen_words(gen + row);
+    if (!(g[kGenFlags] & WGCS_COOKIE_GEN_HAS_MAC1)) return WGCS_ERR_NO_HANDSHAKE;  // cookie.go:323-325
+    uint32_t key[8], ad[4], pt[4];
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-  for (uint32_t i = 0; i < 8; ++i) key[i] = g[kGenKey + i];
+    for (uint32_t i = 0; i < 8; ++i) key[i] = g[kGenKey + i];
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-  for (uint32_t i = 0; i < 4; ++i) ad[i] = g[kGenMac1 + i];
-  if (!xchacha_open16(key, m + 2, m + 8, m + 12, ad, pt)) return WGCS_ERR_AUTH;  // :326-335
-  uint32_t* const w = work + 4 * (uint64_t)q;
+    for (uint32_t i = 0; i < 4; ++i) ad[i] = g[kGenMac1 + i];
+    if (!xchacha_open16(key, m + 2, m + 8, m + 12, ad, pt)) return WGCS_ERR_AUTH;  // :326-335
+    uint32_t* const w = work + 4 * (uint64_t)q;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-  for (uint32_t i = 0; i < 4; ++i) w[i] = pt[i];
-  cookiegen_claim(g + kGenClaim, q + 1);
-  return WGCS_HS_COOKIE_KEPT;
-}
+    for (uint32_t i = 0; i < 4; ++i) w[i] = pt[i];
+    claim_max(g + kGenClaim, q + 1);
+    return WGCS_HS_COOKIE_KEPT;
+  }
+};
 
 // The second pass, row q: the holder of its peer's claim, the highest row that opened, stores
 // its cookie, the valid bit and the time (cookie.go:337-338); every row's work is zeroed.
-WGCS_HD void cookiegen_commit(uint32_t q, const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* verdict,
-                              const CookieGenTables& t, int64_t now, wgcs_cookie_gen* gen, wgcs_hs_peer* peers,
-                              uint32_t* work) {
-  uint32_t* const w = work + 4 * (uint64_t)q;
-  if (verdict[q] == WGCS_HS_COOKIE_KEPT) {
-    // the row the first pass found: no table the lookup reads is written by either pass
-    const uint32_t row = cookiegen_peer_row(cookiegen_msg_receiver(arena + pkts[q].off), t);
-    if (row != WGCS_PEER_NONE) {
-      uint32_t* const g = cookiegen_words(gen + row);
-      if (g[kGenClaim] == q + 1) {  // else a higher row's, or 0 once that row has committed: never q + 1
-        uint32_t* const p = cookiegen_words(peers + row);
+struct CookieCommit {
+  const uint8_t* arena;
+  const wgcs_aead_pkt* pkts;
+  const int32_t* verdict;
+  CookieGenTables t;
+  int64_t now;
+  wgcs_cookie_gen* gen;
+  wgcs_hs_peer* peers;
+  uint32_t* work;
+  WGCS_HD void operator()(uint32_t q) const {
+    uint32_t* const w = work + 4 * (uint64_t)q;
+    if (verdict[q] == WGCS_HS_COOKIE_KEPT) {
+      // the row the first pass found: no table the lookup reads is written by either pass
+      const uint32_t row = cookiegen_peer_row(cookiegen_msg_receiver(arena + pkts[q].off), t);
+      if (row != WGCS_PEER_NONE) {
+        uint32_t* const g = cookiegen_words(gen + row);
+        if (g[kGenClaim] == q + 1) {  // else a higher row's, or 0 once that row has committed: never q + 1
+          uint32_t* const p = cookiegen_words(peers + row);
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-        for (uint32_t i = 0; i < 4; ++i) p[kHsPeerCookie + i] = w[i];
-        p[kHsPeerFlags] |= WGCS_HS_PEER_COOKIE;  // the one lane of this launch that writes the row
-        g[kGenSetAt] = (uint32_t)(uint64_t)now;
-        g[kGenSetAt + 1] = (uint32_t)((uint64_t)now >> 32);
-        g[kGenClaim] = 0;
+          for (uint32_t i = 0; i < 4; ++i) p[kHsPeerCookie + i] = w[i];
+          p[kHsPeerFlags] |= WGCS_HS_PEER_COOKIE;  // the one lane of this launch that writes the row
+          g[kGenSetAt] = (uint32_t)(uint64_t)now;
+          g[kGenSetAt + 1] = (uint32_t)((uint64_t)now >> 32);
+          g[kGenClaim] = 0;
+        }
       }
     }
-  }
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-  for (uint32_t i = 0; i < 4; ++i) w[i] = 0;
-}
+    for (uint32_t i = 0; i < 4; ++i) w[i] = 0;
+  }
+};
 
 // ---- ageing, cookie.go:306: time.Since(cookieSetAt) > CookieRefreshTime, peer row r ----
 
-WGCS_HD void cookiegen_age(uint32_t r, int64_t now, const wgcs_cookie_gen* gen, wgcs_hs_peer* peers) {
-  uint32_t* const p = cookiegen_words(peers + r);
-  const uint32_t flags = p[kHsPeerFlags];
-  if (!(flags & WGCS_HS_PEER_COOKIE)) return;
-  const uint32_t* const g = cookiegen_words(gen + r);
-  const uint64_t set_at = (uint64_t)g[kGenSetAt] | ((uint64_t)g[kGenSetAt + 1] << 32);
-  // signed: a clock that went back gives a negative age, and the cookie stays
-  if ((int64_t)((uint64_t)now - set_at) > WGCS_COOKIE_REFRESH_NS) p[kHsPeerFlags] = flags & ~WGCS_HS_PEER_COOKIE;
-}
+struct CookieAge {
+  int64_t now;
+  const wgcs_cookie_gen* gen;
+  wgcs_hs_peer* peers;
+  WGCS_HD void operator()(uint32_t r) const {
+    uint32_t* const p = cookiegen_words(peers + r);
+    const uint32_t flags = p[kHsPeerFlags];
+    if (!(flags & WGCS_HS_PEER_COOKIE)) return;
+    const uint32_t* const g = cookiegen_words(gen + r);
+    const uint64_t set_at = (uint64_t)g[kGenSetAt] | ((uint64_t)g[kGenSetAt + 1] << 32);
+    // signed: a clock that went back gives a negative age, and the cookie stays
+    if ((int64_t)((uint64_t)now - set_at) > WGCS_COOKIE_REFRESH_NS) p[kHsPeerFlags] = flags & ~WGCS_HS_PEER_COOKIE;
+  }
+};
 
 }  // namespace wgcs

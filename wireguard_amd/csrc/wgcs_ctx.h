@@ -9,7 +9,7 @@
 #include <vector>
 
 #include "../../include/wgcsum.h"
-#include "wgcs_bounds.h"  // kMaxRows, kMaxPeers, overlap
+#include "wgcs_bounds.h"  // kMaxRows, kMaxPeers, pow2_or_0, overlap
 #include "wgcs_kernels.h"
 
 namespace wgcs {
@@ -25,9 +25,8 @@ struct HostBuf {
   size_t cap = 0;
 };
 
-// argument checks of the *_api.cpp files: p is not aligned to mask + 1 bytes; a table size the slot hash can mask
+// argument checks of the *_api.cpp files: p is not aligned to mask + 1 bytes
 inline bool misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
-inline bool pow2_or_0(uint32_t n) { return (n & (n - 1)) == 0; }
 
 int set_err(wgcs_ctx* ctx, int code, const char* fmt, ...);
 int hip_fail(wgcs_ctx* ctx, hipError_t e, const char* what);

@@ -5,9 +5,10 @@
 //   recv        the tail of ReceiveIPvX       conn/bind.go:308-319, conn/sticky.go:46-94
 //   set         SetEndpointFromPacket         device/peer.go:281-286 at receive.go:487, :314, :335
 //   dst         Peer.Send up to bind.Send     peer.go:201-211, with ClearSrc
-// endpoint_kernels.hip runs them one lane per row, endpoint.cpp in row order,
-// udp_msgs_api.cpp takes the walk for wgcs_get_gso_size, and the stand-alone
-// sanitizer program of tests/endpoint_host/ includes this one text.
+// Each pass is a body that wgcs_each.h runs one lane per row and endpoint.cpp in
+// row order, set and dst over the sources of wgcs_events.h; udp_msgs_api.cpp
+// takes the walk for wgcs_get_gso_size, and the stand-alone sanitizer program of
+// tests/endpoint_host/ includes this one text.
 //
 // Several rows of a set call may belong to one peer.  The reference takes them
 // in turn, so the last one's endpoint stands; here every candidate raises the
@@ -161,37 +162,45 @@ WGCS_HD void endpoint_store(wgcs_endpoint* e, const uint32_t row[kEpWords]) {
 
 // ---- bind.go:308-319 for slot q of a receive batch ----
 
-WGCS_HD void endpoint_recv(uint32_t q, uint32_t n_msgs, const wgcs_src_addr* addr, const int32_t* from,
-                           const int32_t* size, const uint8_t* oob, uint32_t oob_stride, const int32_t* nn,
-                           wgcs_endpoint* ep, wgcs_src_addr* addr_out) {
-  uint32_t row[kEpWords];
+struct EndpointRecv {
+  uint32_t n_msgs;
+  const wgcs_src_addr* addr;
+  const int32_t *from, *size;
+  const uint8_t* oob;
+  uint32_t oob_stride;
+  const int32_t* nn;
+  wgcs_endpoint* ep;
+  wgcs_src_addr* addr_out;
+  WGCS_HD void operator()(uint32_t q) const {
+    uint32_t row[kEpWords];
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-  for (uint32_t i = 0; i < kEpWords; ++i) row[i] = 0;
-  const int32_t f = from ? from[q] : -1;
-  if (size[q] != 0 && f >= -1 && f < (int32_t)n_msgs) {  // :311-313: a slot of size 0 gets no endpoint
-    // :314: msg.Addr, which splitMessages copied from message f of the batch (bind.go:570)
-    const uint32_t a = f < 0 ? q : q - q % n_msgs + (uint32_t)f;
-    const uint32_t* const aw = (const uint32_t*)(addr + a);
+    for (uint32_t i = 0; i < kEpWords; ++i) row[i] = 0;
+    const int32_t f = from ? from[q] : -1;
+    if (size[q] != 0 && f >= -1 && f < (int32_t)n_msgs) {  // :311-313: a slot of size 0 gets no endpoint
+      // :314: msg.Addr, which splitMessages copied from message f of the batch (bind.go:570)
+      const uint32_t a = f < 0 ? q : q - q % n_msgs + (uint32_t)f;
+      const uint32_t* const aw = (const uint32_t*)(addr + a);
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-    for (uint32_t i = 0; i < kEpAddrWords; ++i) row[i] = aw[i];
-    // :317: msg.OOB[:msg.NN] of slot q itself
-    const int32_t c = nn[q];
-    const size_t len = c < 0 || (uint32_t)c > oob_stride ? 0 : (size_t)c;
-    endpoint_src_from_control(oob + (uint64_t)q * oob_stride, len, &row[kEpSrcLen], row + kEpSrc);
+      for (uint32_t i = 0; i < kEpAddrWords; ++i) row[i] = aw[i];
+      // :317: msg.OOB[:msg.NN] of slot q itself
+      const int32_t c = nn[q];
+      const size_t len = c < 0 || (uint32_t)c > oob_stride ? 0 : (size_t)c;
+      endpoint_src_from_control(oob + (uint64_t)q * oob_stride, len, &row[kEpSrcLen], row + kEpSrc);
+    }
+    endpoint_store(ep + q, row);
+    if (addr_out) {
+      uint32_t* const o = (uint32_t*)(addr_out + q);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (uint32_t i = 0; i < kEpAddrWords; ++i) o[i] = row[i];
+    }
   }
-  endpoint_store(ep + q, row);
-  if (addr_out) {
-    uint32_t* const o = (uint32_t*)(addr_out + q);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (uint32_t i = 0; i < kEpAddrWords; ++i) o[i] = row[i];
-  }
-}
+};
 
 // ---- SetEndpointFromPacket, peer.go:281-286, in two passes ----
 
@@ -200,187 +209,145 @@ struct EndpointPick {
   uint32_t src;  // the row of ep it takes
 };
 
-// the pick of (row, src) if ep[src] holds an address
-WGCS_HD EndpointPick endpoint_pick(uint32_t row, uint32_t src, const wgcs_endpoint* ep) {
+// the row of ep that entry i of a set call's source brings: receive.go:487 (a tail < 0 lies past n_rows), :314, :335
+WGCS_HD uint32_t endpoint_src(const GroupRows& s, uint32_t c) { return (uint32_t)s.tail(c); }
+WGCS_HD uint32_t endpoint_src(const AcceptedRows& s, uint32_t j) { return s.init_row(j); }
+WGCS_HD uint32_t endpoint_src(const FinishedRows&, uint32_t q) { return q; }
+
+// the pick of entry i: its peer row if its row of ep lies in the table and holds an address
+template <class Rows>
+WGCS_HD EndpointPick endpoint_pick(const Rows& s, uint32_t i, const wgcs_endpoint* ep, uint32_t n_rows) {
+  const uint32_t src = endpoint_src(s, i);
+  if (src >= n_rows) return {WGCS_PEER_NONE, 0};
+  const uint32_t row = s.row(i);
+  if (row == WGCS_PEER_NONE) return {WGCS_PEER_NONE, 0};
   const uint32_t len = endpoint_dst_len(endpoint_words(ep + src)[kEpLenWord]);
   return {len == 6 || len == 18 ? row : WGCS_PEER_NONE, src};
 }
 
-// The row-finders: pick(i) for index i of the call's rows.
-
-struct EndpointReceived {  // receive.go:487 for row c of the write builder's groups
-  const wgcs_write_group* groups;
+// the first pass: candidate i claims its peer's row
+template <class Rows>
+struct EndpointSetClaim {
+  Rows src;
   const wgcs_endpoint* ep;
   uint32_t n_rows;
-  const uint32_t* peer_rows;
-  uint32_t n_ids, n_peers;
-  WGCS_HD EndpointPick pick(uint32_t c) const {
-    const int32_t tail = groups[c].tail;
-    if (tail < 0 || (uint32_t)tail >= n_rows) return {WGCS_PEER_NONE, 0};  // :486: validTailPacket >= 0
-    const uint32_t row = rekey_peer_row(groups[c].peer, peer_rows, n_ids, n_peers);
-    if (row == WGCS_PEER_NONE) return {WGCS_PEER_NONE, 0};
-    return endpoint_pick(row, (uint32_t)tail, ep);
+  uint32_t* claim;
+  WGCS_HD void operator()(uint32_t i) const {
+    const EndpointPick p = endpoint_pick(src, i, ep, n_rows);
+    if (p.row != WGCS_PEER_NONE) claim_max(claim + p.row, i + 1);
   }
 };
-
-struct EndpointAccepted {  // :314 for descriptor j of an accept call
-  const wgcs_hs_resp* resp;
-  const wgcs_endpoint* ep;
-  uint32_t n_rows, n_peers;
-  WGCS_HD EndpointPick pick(uint32_t j) const {
-    const uint32_t src = resp[j].init_row, row = resp[j].peer_row;
-    if (src >= n_rows || row >= n_peers) return {WGCS_PEER_NONE, 0};  // a tail row carries 0xFFFFFFFF
-    return endpoint_pick(row, src, ep);
-  }
-};
-
-struct EndpointFinished {  // :335 for row q of a finish batch
-  const uint8_t* arena;
-  const wgcs_aead_pkt* pkts;
-  const int32_t* gate;
-  const wgcs_session_slot* hs_slots;
-  uint32_t n_hs_slots;
-  const wgcs_hs_state* states;
-  uint32_t n_states;
-  const wgcs_endpoint* ep;
-  uint32_t n_peers;
-  WGCS_HD EndpointPick pick(uint32_t q) const {
-    uint32_t f[4];  // the lookup of timers_finished: receiver -> state row -> peer row
-    if (keypairs_initiator_fields(arena, pkts, gate, q, hs_slots, n_hs_slots, states, n_states, f) != kKeypairsTaken)
-      return {WGCS_PEER_NONE, 0};
-    if (f[0] >= n_peers) return {WGCS_PEER_NONE, 0};
-    return endpoint_pick(f[0], q, ep);
-  }
-};
-
-// *claim = max(*claim, ticket); a plain look first, as cookiegen_claim: the claim only rises within a pass
-WGCS_HD void endpoint_claim(uint32_t* claim, uint32_t ticket) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  if (ticket > __hip_atomic_load(claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(claim, ticket);
-#else
-  if (ticket > *claim) *claim = ticket;
-#endif
-}
-
-// the first pass: candidate i claims its peer's row
-WGCS_HD void endpoint_set_claim(uint32_t i, EndpointPick p, uint32_t* claim) {
-  if (p.row != WGCS_PEER_NONE) endpoint_claim(claim + p.row, i + 1);
-}
 
 // the second pass: the holder of the claim, the highest candidate of its peer, leaves its endpoint
-WGCS_HD void endpoint_set_commit(uint32_t i, EndpointPick p, const wgcs_endpoint* ep, wgcs_endpoint* table,
-                                 uint32_t* claim, wgcs_timers* timers) {
-  if (p.row == WGCS_PEER_NONE) return;
-  if (claim[p.row] != i + 1) return;  // a higher candidate's, or 0 once that one has committed: never i + 1
-  const uint32_t* const s = endpoint_words(ep + p.src);
-  uint32_t* const t = endpoint_words(table + p.row);
+template <class Rows>
+struct EndpointSetCommit {
+  Rows src;
+  const wgcs_endpoint* ep;
+  uint32_t n_rows;
+  wgcs_endpoint* table;
+  uint32_t* claim;
+  wgcs_timers* timers;
+  WGCS_HD void operator()(uint32_t i) const {
+    const EndpointPick p = endpoint_pick(src, i, ep, n_rows);
+    if (p.row == WGCS_PEER_NONE) return;
+    if (claim[p.row] != i + 1) return;  // a higher candidate's, or 0 once that one has committed: never i + 1
+    const uint32_t* const s = endpoint_words(ep + p.src);
+    uint32_t row[kEpWords];  // read whole, then stored: no member says that ep and table are apart
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-  for (uint32_t k = 0; k < kEpWords; ++k) t[k] = s[k];            // peer.go:284
-  timers_and(&timers[p.row].flags, ~WGCS_TIMERS_CLEAR_SRC);       // :285
-  claim[p.row] = 0;
-}
+    for (uint32_t k = 0; k < kEpWords; ++k) row[k] = s[k];
+    endpoint_store(table + p.row, row);                             // peer.go:284
+    timers_and(&timers[p.row].flags, ~WGCS_TIMERS_CLEAR_SRC);       // :285
+    claim[p.row] = 0;
+  }
+};
 
 // ---- Peer.Send up to bind.Send, peer.go:201-211, in two passes ----
 
-// The peer-row finders of the three entry kinds: row(j), WGCS_PEER_NONE for an entry that takes no part.
-
-struct EndpointJobs {  // the rule of timers_sent
-  const uint32_t* peer;
-  const int32_t *count, *status;
-  const uint32_t* job_key;
-  uint32_t max_segs;
-  const uint32_t* peer_rows;
-  uint32_t n_ids, n_peers;
-  WGCS_HD uint32_t row(uint32_t j) const {
-    if (job_key[j] == kRekeyNoKey) return WGCS_PEER_NONE;  // dropped: nothing to send
-    return rekey_job_row(j, peer, count, status, max_segs, peer_rows, n_ids, n_peers);
-  }
-};
-
-struct EndpointInitiated {  // the rule of cookiegen_initiated_row
-  const wgcs_hs_start* start;
-  const int32_t* status;
-  uint32_t n_peers;
-  WGCS_HD uint32_t row(uint32_t j) const {
-    if (status[j] != WGCS_HS_INITIATED) return WGCS_PEER_NONE;
-    const uint32_t r = start[j].peer_row;
-    return r < n_peers ? r : WGCS_PEER_NONE;
-  }
-};
-
-struct EndpointResponded {  // the rule of cookiegen_responded_row
-  const wgcs_hs_resp* resp;
-  const int32_t* status;
-  uint32_t n_peers;
-  WGCS_HD uint32_t row(uint32_t j) const {
-    if (status[j] != WGCS_HS_RESPONDED) return WGCS_PEER_NONE;
-    const uint32_t r = resp[j].peer_row;
-    return r < n_peers ? r : WGCS_PEER_NONE;
-  }
-};
-
-// The first pass, entry j whose peer row is `row`: d_dst[j], d_dst_v6[j] and the status, which is
-// returned too.  Neither table is written.
-WGCS_HD int32_t endpoint_dst_read(uint32_t j, uint32_t row, const wgcs_endpoint* table, const wgcs_timers* timers,
-                                  wgcs_endpoint* dst, int32_t* dst_v6, int32_t* dst_status) {
-  uint32_t out[kEpWords];
+// The first pass, entry j: d_dst[j], d_dst_v6[j] and the status, which read() returns too.
+// Neither table is written.
+template <class Rows>
+struct EndpointDstRead {
+  Rows src;
+  const wgcs_endpoint* table;
+  const wgcs_timers* timers;
+  wgcs_endpoint* dst;
+  int32_t *dst_v6, *dst_status;
+  WGCS_HD void operator()(uint32_t j) const { read(j, src.row(j)); }
+  WGCS_HD int32_t read(uint32_t j, uint32_t row) const {
+    uint32_t out[kEpWords];
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-  for (uint32_t i = 0; i < kEpWords; ++i) out[i] = 0;
-  int32_t status = WGCS_OK, v6 = 0;
-  if (row != WGCS_PEER_NONE) {
-    const uint32_t* const t = endpoint_words(table + row);
-    const uint32_t len = endpoint_dst_len(t[kEpLenWord]);
-    if (len == 0) {
-      status = WGCS_ERR_NO_ENDPOINT;  // peer.go:202-205: returns before clearSrcOnTx is looked at
-    } else {
-      const bool clear = (timers[row].flags & WGCS_TIMERS_CLEAR_SRC) != 0;  // :206-209
+    for (uint32_t i = 0; i < kEpWords; ++i) out[i] = 0;
+    int32_t status = WGCS_OK, v6 = 0;
+    if (row != WGCS_PEER_NONE) {
+      const uint32_t* const t = endpoint_words(table + row);
+      const uint32_t len = endpoint_dst_len(t[kEpLenWord]);
+      if (len == 0) {
+        status = WGCS_ERR_NO_ENDPOINT;  // peer.go:202-205: returns before clearSrcOnTx is looked at
+      } else {
+        const bool clear = (timers[row].flags & WGCS_TIMERS_CLEAR_SRC) != 0;  // :206-209
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-      for (uint32_t i = 0; i < kEpWords; ++i) out[i] = clear && i >= kEpSrcLen ? 0u : t[i];
-      v6 = len == 18;  // DstIP().Is6(): every 16-byte address, conn/bind.go:405
+        for (uint32_t i = 0; i < kEpWords; ++i) out[i] = clear && i >= kEpSrcLen ? 0u : t[i];
+        v6 = len == 18;  // DstIP().Is6(): every 16-byte address, conn/bind.go:405
+      }
     }
+    endpoint_store(dst + j, out);
+    dst_v6[j] = v6;
+    dst_status[j] = status;
+    return status;
   }
-  endpoint_store(dst + j, out);
-  dst_v6[j] = v6;
-  dst_status[j] = status;
-  return status;
-}
+};
+
+// The first pass of the send jobs' form: no message for a job without an endpoint, and the
+// bytes of peer.go:213-218 for one with a destination.
+struct EndpointDstJobs {
+  EndpointDstRead<KeptJobRows> rd;
+  const int32_t* lens;
+  int32_t* nbufs;
+  uint64_t* tx_bytes;
+  WGCS_HD void operator()(uint32_t j) const {
+    const uint32_t row = rd.src.row(j);
+    const int32_t status = rd.read(j, row);
+    const uint32_t max_segs = rd.src.jobs.max_segs;
+    uint64_t tx = 0;
+    if (status == WGCS_ERR_NO_ENDPOINT) {
+      nbufs[j] = 0;
+    } else if (row != WGCS_PEER_NONE) {
+      const int32_t nb = nbufs[j];
+      const uint32_t n = nb < 0 ? 0u : (uint32_t)nb > max_segs ? max_segs : (uint32_t)nb;
+      const int32_t* const l = lens + (uint64_t)j * max_segs;
+      for (uint32_t k = 0; k < n; ++k) tx += l[k] > 0 ? (uint64_t)l[k] : 0u;
+    }
+    tx_bytes[j] = tx;
+  }
+};
 
 // The second pass: ClearSrc on the table row of a peer the first pass gave a cleared source, and
 // clearSrcOnTx = false.  Every entry of the peer stores the same zeros.
-WGCS_HD void endpoint_dst_clear(uint32_t row, wgcs_endpoint* table, wgcs_timers* timers) {
-  if (row == WGCS_PEER_NONE) return;
-  uint32_t* const t = endpoint_words(table + row);
-  if (endpoint_dst_len(t[kEpLenWord]) == 0) return;  // no endpoint: the flag stays
-  if (!(timers[row].flags & WGCS_TIMERS_CLEAR_SRC)) return;
+template <class Rows>
+struct EndpointDstClear {
+  Rows src;
+  wgcs_endpoint* table;
+  wgcs_timers* timers;
+  WGCS_HD void operator()(uint32_t j) const {
+    const uint32_t row = src.row(j);
+    if (row == WGCS_PEER_NONE) return;
+    uint32_t* const t = endpoint_words(table + row);
+    if (endpoint_dst_len(t[kEpLenWord]) == 0) return;  // no endpoint: the flag stays
+    if (!(timers[row].flags & WGCS_TIMERS_CLEAR_SRC)) return;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-  for (uint32_t i = kEpSrcLen; i < kEpWords; ++i)
-    if (t[i] != 0) t[i] = 0;
-  timers_and(&timers[row].flags, ~WGCS_TIMERS_CLEAR_SRC);
-}
-
-// What a send job adds to the first pass: no message for a job without an endpoint, and the
-// bytes of peer.go:213-218 for one with a destination.
-WGCS_HD void endpoint_dst_job(uint32_t j, uint32_t row, int32_t status, uint32_t max_segs, const int32_t* lens,
-                              int32_t* nbufs, uint64_t* tx_bytes) {
-  uint64_t tx = 0;
-  if (status == WGCS_ERR_NO_ENDPOINT) {
-    nbufs[j] = 0;
-  } else if (row != WGCS_PEER_NONE) {
-    const int32_t nb = nbufs[j];
-    const uint32_t n = nb < 0 ? 0u : (uint32_t)nb > max_segs ? max_segs : (uint32_t)nb;
-    const int32_t* const l = lens + (uint64_t)j * max_segs;
-    for (uint32_t k = 0; k < n; ++k) tx += l[k] > 0 ? (uint64_t)l[k] : 0u;
+    for (uint32_t i = kEpSrcLen; i < kEpWords; ++i)
+      if (t[i] != 0) t[i] = 0;
+    timers_and(&timers[row].flags, ~WGCS_TIMERS_CLEAR_SRC);
   }
-  tx_bytes[j] = tx;
-}
+};
 
 // ---- the argument rules the device entry points and the host forms share (host code) ----
 

@@ -162,53 +162,25 @@ hipError_t launch_keypairs_received(const wgcs_aead_pkt* pkts, const int32_t* ve
                                     wgcs_session_slot* peer_keys, uint32_t n_peer_slots, wgcs_aead_key* keys,
                                     uint32_t* rotated, hipStream_t s);
 
-// Keypair expiry, the rekey rules and the start of a handshake (rekey_kernels.hip, the row
-// functions of wgcs_rekey.h): one launch each, one lane per row, but launch_rekey_start, which
-// is the scheme of wgcs_compact.h over the peer rows, the candidates flagged.
-hipError_t launch_rekey_recv_gate(wgcs_aead_pkt* pkts, uint32_t n, int64_t now, const uint32_t* key_peer,
-                                  uint32_t n_keys, const uint32_t* peer_rows, uint32_t n_ids, const wgcs_keypairs* kp,
-                                  uint32_t n_peers, hipStream_t s);
-hipError_t launch_rekey_send_gate(const uint32_t* peer, const int32_t* count, const int32_t* status_in, uint32_t n_jobs,
-                                  uint32_t max_segs, int64_t now, const uint32_t* peer_rows, uint32_t n_ids,
-                                  const wgcs_keypairs* kp, uint32_t n_peers, const uint64_t* send_nonce,
-                                  uint32_t n_keys, uint64_t limit, wgcs_rekey* rekey, int32_t* status_out,
-                                  hipStream_t s);
-hipError_t launch_rekey_sent(const uint32_t* peer, const int32_t* count, const int32_t* status, const uint32_t* job_key,
-                             uint32_t n_jobs, uint32_t max_segs, int64_t now, const uint32_t* peer_rows,
-                             uint32_t n_ids, const wgcs_keypairs* kp, uint32_t n_peers, const uint64_t* send_nonce,
-                             uint32_t n_keys, uint64_t limit, wgcs_rekey* rekey, hipStream_t s);
-hipError_t launch_rekey_received(const wgcs_write_group* groups, uint32_t n, int64_t now, const uint32_t* peer_rows,
-                                 uint32_t n_ids, const wgcs_keypairs* kp, uint32_t n_peers, wgcs_rekey* rekey,
-                                 hipStream_t s);
-hipError_t launch_rekey_responded(const wgcs_hs_resp* resp, const int32_t* gate, uint32_t n, int64_t now,
-                                  wgcs_rekey* rekey, uint32_t n_peers, hipStream_t s);
+// One lane per entry (wgcs_each.h): the body f, a struct with operator()(uint32_t), for every
+// i < n, and the two passes of a claim-and-commit call, the second launched behind the first on
+// s.  n is not 0.  The event calls of the timers, the rekey rules, the cookie generator and the
+// endpoints are such bodies (wgcs_timers.h, wgcs_rekey.h, wgcs_cookiegen.h, wgcs_endpoint.h),
+// instantiated in their families' .hip files.
+template <class F>
+hipError_t launch_each(const F& f, uint32_t n, hipStream_t s);
+template <class F, class G>
+hipError_t launch_each(const F& first, const G& second, uint32_t n, hipStream_t s);
+
+// The start of a handshake (rekey_kernels.hip, the row functions of wgcs_rekey.h): the scheme of
+// wgcs_compact.h over the peer rows, the candidates flagged.
 hipError_t launch_rekey_start(int64_t now, wgcs_rekey* rekey, const wgcs_hs_peer* hs_peers, uint32_t n_peers,
                               const wgcs_hs_start* tickets, uint32_t n_tickets, wgcs_hs_start* start,
                               uint32_t* start_peer, uint32_t* count, int32_t* status, uint32_t* reasons,
                               uint32_t* block_cand, hipStream_t s);
 
-// The peer timers (timers_kernels.hip, the row functions of wgcs_timers.h): one launch each, one
-// lane per row, but launch_timers_initiated (the peer rows, then the tickets) and
-// launch_timers_expire, which is the scheme of wgcs_compact.h over the peer rows, those that owe
-// a keepalive job flagged.
-hipError_t launch_timers_sent(const int32_t* sizes, const uint32_t* peer, const int32_t* count, const int32_t* status,
-                              const uint32_t* job_key, uint32_t n_jobs, uint32_t max_segs, int64_t now, uint32_t seed,
-                              const uint32_t* peer_rows, uint32_t n_ids, wgcs_timers* timers, uint32_t n_peers,
-                              hipStream_t s);
-hipError_t launch_timers_received(const wgcs_write_group* groups, uint32_t n, int64_t now, const uint32_t* peer_rows,
-                                  uint32_t n_ids, wgcs_timers* timers, uint32_t n_peers, hipStream_t s);
-hipError_t launch_timers_initiated(const uint32_t* reasons, const uint32_t* start_peer, const int32_t* init_status,
-                                   uint32_t n_tickets, int64_t now, uint32_t seed, wgcs_timers* timers,
-                                   uint32_t n_peers, hipStream_t s);
-hipError_t launch_timers_responded(const wgcs_hs_resp* resp, const int32_t* gate, uint32_t n, int64_t now,
-                                   wgcs_timers* timers, uint32_t n_peers, hipStream_t s);
-hipError_t launch_timers_finished(const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* gate,
-                                  const int32_t* begun, uint32_t n, int64_t now, const wgcs_session_slot* hs_slots,
-                                  uint32_t n_hs_slots, const wgcs_hs_state* states, uint32_t n_states,
-                                  wgcs_timers* timers, wgcs_rekey* rekey, uint32_t n_peers, hipStream_t s);
-hipError_t launch_timers_rotated(const wgcs_aead_pkt* pkts, const uint32_t* rotated, uint32_t n, int64_t now,
-                                 const uint32_t* key_peer, uint32_t n_keys, const uint32_t* peer_rows, uint32_t n_ids,
-                                 wgcs_timers* timers, wgcs_rekey* rekey, uint32_t n_peers, hipStream_t s);
+// The expiry of the peer timers (timers_kernels.hip, the row functions of wgcs_timers.h): the
+// scheme of wgcs_compact.h over the peer rows, those that owe a keepalive job flagged.
 hipError_t launch_timers_expire(int64_t now, wgcs_timers* timers, wgcs_rekey* rekey, const wgcs_peer_key* table,
                                 uint32_t n_peers, const uint32_t* staged, wgcs_keypairs* kp, wgcs_session_slot* slots,
                                 uint32_t n_slots, wgcs_session_slot* peer_keys, uint32_t n_peer_slots,
@@ -225,20 +197,6 @@ hipError_t launch_ratelimit(const KeyOrder& ko, const int32_t* gate, const wgcs_
                             hipStream_t s);
 hipError_t launch_ratelimit_cleanup(const wgcs_rl_entry* old_table, wgcs_rl_entry* new_table, uint32_t n_slots,
                                     int64_t now, uint32_t* live, hipStream_t s);
-
-// The cookie generator (cookiegen_kernels.hip, the row functions of wgcs_cookiegen.h), one lane
-// per row: initiated, responded and consume are a claim launch and a commit launch each, age one
-// launch over the peer rows.  The row count of a call is not 0.
-struct CookieGenTables;  // wgcs_cookiegen.h
-hipError_t launch_cookie_initiated(const wgcs_hs_start* start, const int32_t* status, const uint8_t* msgs, uint32_t n,
-                                   wgcs_cookie_gen* gen, uint32_t n_peers, hipStream_t s);
-hipError_t launch_cookie_responded(const wgcs_hs_resp* resp, const int32_t* status, const uint8_t* msgs, uint32_t n,
-                                   wgcs_cookie_gen* gen, uint32_t n_peers, hipStream_t s);
-hipError_t launch_cookie_consume(const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* types, uint32_t n,
-                                 int64_t now, const CookieGenTables& t, wgcs_cookie_gen* gen, wgcs_hs_peer* peers,
-                                 uint32_t* work, int32_t* verdict, hipStream_t s);
-hipError_t launch_cookie_age(int64_t now, const wgcs_cookie_gen* gen, wgcs_hs_peer* peers, uint32_t n_peers,
-                             hipStream_t s);
 
 // The staged queue (staged_kernels.hip, the row functions of wgcs_staged.h).  Stage: the jobs'
 // rows as keys and a count of them, the key order over the peer rows on a carved workspace, one
@@ -264,34 +222,5 @@ hipError_t launch_staged_release(int64_t now, const wgcs_peer_key* table, const 
                                  int32_t* status, uint32_t* work, hipStream_t s);
 hipError_t launch_staged_flush(const uint32_t* actions, uint32_t* len, uint32_t* head, uint32_t* lost, uint32_t n_peers,
                                hipStream_t s);
-
-// The peer endpoints (endpoint_kernels.hip, the row functions of wgcs_endpoint.h), one lane per
-// row: recv is one launch; a set call is a claim launch and a commit launch, a dst call a read
-// launch and a clear launch, each templated on the finder (wgcs_endpoint.h) that names a row's
-// peer.  The row count of a call is not 0.
-struct EndpointReceived;
-struct EndpointAccepted;
-struct EndpointFinished;
-struct EndpointJobs;
-struct EndpointInitiated;
-struct EndpointResponded;
-hipError_t launch_endpoint_recv(const wgcs_src_addr* addr, const int32_t* from, const int32_t* size, const uint8_t* oob,
-                                uint32_t oob_stride, const int32_t* nn, uint32_t n_msgs, uint32_t n, wgcs_endpoint* ep,
-                                wgcs_src_addr* addr_out, hipStream_t s);
-hipError_t launch_endpoint_set_received(const EndpointReceived& f, uint32_t n, wgcs_endpoint* table, uint32_t* claim,
-                                        wgcs_timers* timers, hipStream_t s);
-hipError_t launch_endpoint_set_accepted(const EndpointAccepted& f, uint32_t n, wgcs_endpoint* table, uint32_t* claim,
-                                        wgcs_timers* timers, hipStream_t s);
-hipError_t launch_endpoint_set_finished(const EndpointFinished& f, uint32_t n, wgcs_endpoint* table, uint32_t* claim,
-                                        wgcs_timers* timers, hipStream_t s);
-hipError_t launch_endpoint_dst_jobs(const EndpointJobs& f, uint32_t n_jobs, const int32_t* lens, int32_t* nbufs,
-                                    wgcs_endpoint* table, wgcs_timers* timers, wgcs_endpoint* dst, int32_t* dst_v6,
-                                    int32_t* dst_status, uint64_t* tx_bytes, hipStream_t s);
-hipError_t launch_endpoint_dst_initiated(const EndpointInitiated& f, uint32_t n, wgcs_endpoint* table,
-                                         wgcs_timers* timers, wgcs_endpoint* dst, int32_t* dst_v6, int32_t* dst_status,
-                                         hipStream_t s);
-hipError_t launch_endpoint_dst_responded(const EndpointResponded& f, uint32_t n, wgcs_endpoint* table,
-                                         wgcs_timers* timers, wgcs_endpoint* dst, int32_t* dst_v6, int32_t* dst_status,
-                                         hipStream_t s);
 
 }  // namespace wgcs

@@ -6,8 +6,10 @@
 //   keepKeyFreshReceiving      receive.go:80-91 (called at :486-488)
 //   SendHandshakeResponse      send.go:131-133, its lastSentHandshake alone
 //   SendHandshakeInitiation    send.go:84-100, up to CreateMessageInitiation
-// rekey_kernels.hip runs them one lane per row, rekey.cpp in row order, and the
-// stand-alone sanitizer program of tests/rekey_host/ includes this one text.
+// The five per-entry calls are bodies over the sources of wgcs_events.h, which
+// wgcs_each.h runs one lane per entry; rekey_kernels.hip runs the start call one
+// lane per row, rekey.cpp all of it in row order, and the stand-alone sanitizer
+// program of tests/rekey_host/ includes this one text.
 //
 // The tables are those of include/wgcsum.h: one wgcs_rekey row beside every
 // wgcs_keypairs row, found from a peer id through wgcs_peer_rows_build's rows.
@@ -21,20 +23,11 @@
 #include <stdint.h>
 
 #include "../../include/wgcsum.h"
-#include "wgcs_route_walk.h"
+#include "wgcs_events.h"
 
 namespace wgcs {
 
-constexpr uint32_t kRekeyNoKey = 0xFFFFFFFFu;  // send-assign's d_job_key of a dropped job
-
 static_assert(sizeof(wgcs_rekey) == 16 && sizeof(wgcs_hs_start) == 96 && sizeof(wgcs_hs_peer) == 64, "row layouts");
-
-// the row of the peer table that id names, or WGCS_PEER_NONE for "no row"
-WGCS_HD uint32_t rekey_peer_row(uint32_t id, const uint32_t* peer_rows, uint32_t n_ids, uint32_t n_peers) {
-  if (id >= n_ids) return WGCS_PEER_NONE;
-  const uint32_t row = peer_rows[id];
-  return row < n_peers ? row : WGCS_PEER_NONE;  // n_peers <= 2^24: WGCS_PEER_NONE itself is past it
-}
 
 WGCS_HD void rekey_want_or(wgcs_rekey* r, uint32_t bits) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -50,34 +43,28 @@ WGCS_HD bool rekey_ref_receives(const wgcs_keypair_ref* r, uint32_t key) {
   return (r->flags & WGCS_KEYPAIR_SET) && r->recv_key == key;
 }
 
-// true: row i's key is the receive key of one of its peer's three keypairs, and that keypair
-// is past RejectAfterTime (createdAt.Add(RejectAfterTime).Before(now): equality passes)
-WGCS_HD bool rekey_recv_expired(uint32_t i, const wgcs_aead_pkt* pkts, int64_t now, const uint32_t* key_peer,
-                                uint32_t n_keys, const uint32_t* peer_rows, uint32_t n_ids, const wgcs_keypairs* kp,
-                                uint32_t n_peers) {
-  const uint32_t key = pkts[i].key;
-  if (key >= n_keys) return false;
-  const uint32_t row = rekey_peer_row(key_peer[key], peer_rows, n_ids, n_peers);
-  if (row == WGCS_PEER_NONE) return false;
-  const wgcs_keypairs* const k = kp + row;
-  const wgcs_keypair_ref* ref = nullptr;  // sessions.Get(receiver).keypair
-  if (rekey_ref_receives(&k->current, key)) ref = &k->current;
-  else if (rekey_ref_receives(&k->previous, key)) ref = &k->previous;
-  else if (rekey_ref_receives(&k->next, key)) ref = &k->next;
-  return ref && now - ref->created_ns > WGCS_REJECT_AFTER_TIME_NS;
-}
+// Row i's key is the receive key of one of its peer's three keypairs, and that keypair is past
+// RejectAfterTime (createdAt.Add(RejectAfterTime).Before(now): equality passes): the packet is
+// turned away.  src reads pkts[i].key and only lane i writes it, behind its own read.
+struct RekeyRecvGate {
+  KeyRows src;
+  int64_t now;
+  const wgcs_keypairs* kp;
+  wgcs_aead_pkt* pkts;  // src.pkts
+  WGCS_HD void operator()(uint32_t i) const {
+    const uint32_t row = src.row(i);
+    if (row == WGCS_PEER_NONE) return;
+    const uint32_t key = src.key(i);
+    const wgcs_keypairs* const k = kp + row;
+    const wgcs_keypair_ref* ref = nullptr;  // sessions.Get(receiver).keypair
+    if (rekey_ref_receives(&k->current, key)) ref = &k->current;
+    else if (rekey_ref_receives(&k->previous, key)) ref = &k->previous;
+    else if (rekey_ref_receives(&k->next, key)) ref = &k->next;
+    if (ref && now - ref->created_ns > WGCS_REJECT_AFTER_TIME_NS) pkts[i].key = WGCS_SESSION_EXPIRED;
+  }
+};
 
 // ---- the send side: the gate in front of send-assign and keepKeyFreshSending behind it ----
-
-// The peer row of job j by send-assign's own rule (status 0, 1 <= count <= max_segs, the first
-// slot's peer), or WGCS_PEER_NONE for a job that is not taken or whose peer has no row.
-WGCS_HD uint32_t rekey_job_row(uint32_t j, const uint32_t* peer, const int32_t* count, const int32_t* status,
-                               uint32_t max_segs, const uint32_t* peer_rows, uint32_t n_ids, uint32_t n_peers) {
-  if (status[j] != 0) return WGCS_PEER_NONE;
-  const int32_t c = count[j];
-  if (c < 1 || (uint32_t)c > max_segs) return WGCS_PEER_NONE;
-  return rekey_peer_row(peer[(uint64_t)j * max_segs], peer_rows, n_ids, n_peers);
-}
 
 // send.go:369-371 for peer row `row`: the reasons its current keypair cannot send, 0 for one that can.
 // The staged queue's release asks the same question per row (wgcs_staged.h).
@@ -93,72 +80,95 @@ WGCS_HD uint32_t rekey_gate_want(uint32_t row, int64_t now, const wgcs_keypairs*
   return w;
 }
 
-// send.go:368-374: what send-assign reads as job j's status
-WGCS_HD int32_t rekey_send_gate(uint32_t j, const uint32_t* peer, const int32_t* count, const int32_t* status_in,
-                                uint32_t max_segs, int64_t now, const uint32_t* peer_rows, uint32_t n_ids,
-                                const wgcs_keypairs* kp, uint32_t n_peers, const uint64_t* send_nonce, uint32_t n_keys,
-                                uint64_t limit, wgcs_rekey* rekey) {
-  const int32_t st = status_in[j];
-  const uint32_t row = rekey_job_row(j, peer, count, status_in, max_segs, peer_rows, n_ids, n_peers);
-  if (row == WGCS_PEER_NONE) return st;
-  const uint32_t w = rekey_gate_want(row, now, kp, send_nonce, n_keys, limit);
-  if (w == 0) return st;
-  rekey_want_or(rekey + row, w);  // :372
-  return WGCS_ERR_KEY_EXPIRED;    // :373: the job stays staged
-}
+// send.go:368-374: what send-assign reads as job j's status.  status_out may be src.status: a
+// lane reads its own word and then writes it.
+struct RekeySendGate {
+  JobRows src;
+  int64_t now;
+  const wgcs_keypairs* kp;
+  const uint64_t* send_nonce;
+  uint32_t n_keys;
+  uint64_t limit;
+  wgcs_rekey* rekey;
+  int32_t* status_out;
+  WGCS_HD void operator()(uint32_t j) const {
+    int32_t st = src.status[j];
+    const uint32_t row = src.row(j);
+    const uint32_t w = row == WGCS_PEER_NONE ? 0u : rekey_gate_want(row, now, kp, send_nonce, n_keys, limit);
+    if (w != 0) {
+      rekey_want_or(rekey + row, w);  // :372
+      st = WGCS_ERR_KEY_EXPIRED;      // :373: the job stays staged
+    }
+    status_out[j] = st;
+  }
+};
 
 // keepKeyFreshSending (send.go:213-227) for a kept job, the goto top of :419-420 for a dropped one
-WGCS_HD void rekey_sent(uint32_t j, const uint32_t* peer, const int32_t* count, const int32_t* status,
-                        const uint32_t* job_key, uint32_t max_segs, int64_t now, const uint32_t* peer_rows,
-                        uint32_t n_ids, const wgcs_keypairs* kp, uint32_t n_peers, const uint64_t* send_nonce,
-                        uint32_t n_keys, uint64_t limit, wgcs_rekey* rekey) {
-  const uint32_t row = rekey_job_row(j, peer, count, status, max_segs, peer_rows, n_ids, n_peers);
-  if (row == WGCS_PEER_NONE) return;
-  const wgcs_keypair_ref* const cur = &kp[row].current;
-  if (!(cur->flags & WGCS_KEYPAIR_SET)) return;  // :215-217
-  const bool has_nonce = cur->send_key < n_keys;
-  const uint64_t nonce = has_nonce ? send_nonce[cur->send_key] : 0;
-  uint32_t w = 0;
-  if (job_key[j] != kRekeyNoKey) {
-    if (nonce > WGCS_REKEY_AFTER_MESSAGES) w |= WGCS_REKEY_WANT_REKEY_MESSAGES;  // :223
-    if ((cur->flags & WGCS_KEYPAIR_INITIATOR) && now - cur->created_ns > WGCS_REKEY_AFTER_TIME_NS)
-      w |= WGCS_REKEY_WANT_REKEY_TIME;  // :224
-  } else if (has_nonce && nonce >= limit) {
-    w |= WGCS_REKEY_WANT_REJECT_MESSAGES;  // :385-390, :419-420 and then :370
+struct RekeySent {
+  JobRows src;
+  const uint32_t* job_key;
+  int64_t now;
+  const wgcs_keypairs* kp;
+  const uint64_t* send_nonce;
+  uint32_t n_keys;
+  uint64_t limit;
+  wgcs_rekey* rekey;
+  WGCS_HD void operator()(uint32_t j) const {
+    const uint32_t row = src.row(j);
+    if (row == WGCS_PEER_NONE) return;
+    const wgcs_keypair_ref* const cur = &kp[row].current;
+    if (!(cur->flags & WGCS_KEYPAIR_SET)) return;  // :215-217
+    const bool has_nonce = cur->send_key < n_keys;
+    const uint64_t nonce = has_nonce ? send_nonce[cur->send_key] : 0;
+    uint32_t w = 0;
+    if (job_kept(job_key, j)) {
+      if (nonce > WGCS_REKEY_AFTER_MESSAGES) w |= WGCS_REKEY_WANT_REKEY_MESSAGES;  // :223
+      if ((cur->flags & WGCS_KEYPAIR_INITIATOR) && now - cur->created_ns > WGCS_REKEY_AFTER_TIME_NS)
+        w |= WGCS_REKEY_WANT_REKEY_TIME;  // :224
+    } else if (has_nonce && nonce >= limit) {
+      w |= WGCS_REKEY_WANT_REJECT_MESSAGES;  // :385-390, :419-420 and then :370
+    }
+    if (w) rekey_want_or(rekey + row, w);
   }
-  if (w) rekey_want_or(rekey + row, w);
-}
+};
 
 // ---- keepKeyFreshReceiving, receive.go:80-91, for one row of the write builder's groups ----
 
-WGCS_HD void rekey_received(uint32_t c, const wgcs_write_group* groups, int64_t now, const uint32_t* peer_rows,
-                            uint32_t n_ids, const wgcs_keypairs* kp, uint32_t n_peers, wgcs_rekey* rekey) {
-  if (groups[c].tail < 0) return;  // receive.go:486: no valid tail packet
-  const uint32_t row = rekey_peer_row(groups[c].peer, peer_rows, n_ids, n_peers);
-  if (row == WGCS_PEER_NONE) return;
-  const wgcs_keypair_ref* const cur = &kp[row].current;
-  const uint32_t both = WGCS_KEYPAIR_SET | WGCS_KEYPAIR_INITIATOR;
-  if ((cur->flags & both) != both) return;  // :85-86
-  if (!(now - cur->created_ns > WGCS_REJECT_AFTER_TIME_NS - WGCS_KEEPALIVE_TIMEOUT_NS - WGCS_REKEY_TIMEOUT_NS))
-    return;  // :87
-  wgcs_rekey* const r = rekey + row;
+struct RekeyReceived {
+  GroupRows src;
+  int64_t now;
+  const wgcs_keypairs* kp;
+  wgcs_rekey* rekey;
+  WGCS_HD void operator()(uint32_t c) const {
+    const uint32_t row = src.row(c);  // receive.go:486: no valid tail packet, no call
+    if (row == WGCS_PEER_NONE) return;
+    const wgcs_keypair_ref* const cur = &kp[row].current;
+    const uint32_t both = WGCS_KEYPAIR_SET | WGCS_KEYPAIR_INITIATOR;
+    if ((cur->flags & both) != both) return;  // :85-86
+    if (!(now - cur->created_ns > WGCS_REJECT_AFTER_TIME_NS - WGCS_KEEPALIVE_TIMEOUT_NS - WGCS_REKEY_TIMEOUT_NS))
+      return;  // :87
+    wgcs_rekey* const r = rekey + row;
 #if defined(__HIP_DEVICE_COMPILE__)
-  const uint32_t old = atomicOr(&r->flags, WGCS_REKEY_LAST_MINUTE);  // :81, :88
+    const uint32_t old = atomicOr(&r->flags, WGCS_REKEY_LAST_MINUTE);  // :81, :88
 #else
-  const uint32_t old = r->flags;
-  r->flags = old | WGCS_REKEY_LAST_MINUTE;
+    const uint32_t old = r->flags;
+    r->flags = old | WGCS_REKEY_LAST_MINUTE;
 #endif
-  if (!(old & WGCS_REKEY_LAST_MINUTE)) rekey_want_or(r, WGCS_REKEY_WANT_LAST_MINUTE);  // :89
-}
+    if (!(old & WGCS_REKEY_LAST_MINUTE)) rekey_want_or(r, WGCS_REKEY_WANT_LAST_MINUTE);  // :89
+  }
+};
 
 // ---- SendHandshakeResponse's lastSentHandshake, send.go:131-133 ----
 
-WGCS_HD void rekey_responded(uint32_t j, const wgcs_hs_resp* resp, const int32_t* gate, int64_t now, wgcs_rekey* rekey,
-                             uint32_t n_peers) {
-  if (gate[j] != WGCS_HS_RESPONDED) return;
-  const uint32_t row = resp[j].peer_row;
-  if (row < n_peers) rekey[row].last_sent_ns = now;
-}
+struct RekeyResponded {
+  RespondedRows src;
+  int64_t now;
+  wgcs_rekey* rekey;
+  WGCS_HD void operator()(uint32_t j) const {
+    const uint32_t row = src.row(j);
+    if (row != WGCS_PEER_NONE) rekey[row].last_sent_ns = now;
+  }
+};
 
 // ---- SendHandshakeInitiation, send.go:84-100, over the peer rows in three passes ----
 

@@ -47,7 +47,7 @@ WGCS_HD uint32_t staged_job_row(uint32_t j, const uint32_t* peer, const int32_t*
                                 const uint32_t* peer_rows, uint32_t n_ids, uint32_t n_peers) {
   const int32_t so = status_out[j];
   if (so != WGCS_ERR_KEY_EXPIRED && !(so == 0 && job_key[j] == kRekeyNoKey)) return WGCS_PEER_NONE;
-  return rekey_job_row(j, peer, count, status_in, max_segs, peer_rows, n_ids, n_peers);
+  return JobRows{peer, count, status_in, max_segs, peer_rows, n_ids, n_peers}.row(j);
 }
 
 // the packets among segments [0, s) of job j (count[j] checked by staged_job_row) that a slot can hold

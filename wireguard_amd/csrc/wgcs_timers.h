@@ -8,8 +8,10 @@
 //   finished     receive.go:339-348         ... session derived, complete, SendKeepalive
 //   rotated      receive.go:422-427         complete
 // and the five expiry bodies of timers.go:73-144 with peer.go:246-251.
-// timers_kernels.hip runs them one lane per row, timers.cpp in row order, and the
-// stand-alone sanitizer program of tests/timers_host/ includes this one text.
+// The event calls are bodies over the sources of wgcs_events.h, which wgcs_each.h
+// runs one lane per entry; timers_kernels.hip runs the expiry one lane per row,
+// timers.cpp all of it in row order, and the stand-alone sanitizer program of
+// tests/timers_host/ includes this one text.
 //
 // Several rows of an event call may belong to one peer.  They OR bits into or
 // AND bits out of pending and flags, never both for one bit in one call, and
@@ -23,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/wgcsum.h"
+#include "wgcs_events.h"
 #include "wgcs_keypairs.h"
 #include "wgcs_rekey.h"
 
@@ -135,96 +138,112 @@ WGCS_HD void timers_handshake_complete(wgcs_timers* t, wgcs_rekey* r, int64_t no
   t->last_handshake_ns = now;
 }
 
-// ---- the event calls, one row each ----
+// ---- the event calls: one body each over its source (wgcs_events.h), entry i ----
 
-// send.go:498-510 for job j of a send-assign batch
-WGCS_HD void timers_sent(uint32_t j, const int32_t* sizes, const uint32_t* peer, const int32_t* count,
-                         const int32_t* status, const uint32_t* job_key, uint32_t max_segs, int64_t now, uint32_t seed,
-                         const uint32_t* peer_rows, uint32_t n_ids, wgcs_timers* timers, uint32_t n_peers) {
-  if (job_key[j] == kRekeyNoKey) return;  // dropped: nothing was sent
-  const uint32_t row = rekey_job_row(j, peer, count, status, max_segs, peer_rows, n_ids, n_peers);
-  if (row == WGCS_PEER_NONE) return;
-  bool data_sent = false;  // :498-502: a keepalive's slot has size 0
-  const int32_t* const sz = sizes + (uint64_t)j * max_segs;
-  for (int32_t k = 0; k < count[j]; ++k) data_sent |= sz[k] != 0;
-  wgcs_timers* const t = timers + row;
-  timers_traversal(t, now);  // :505
-  timers_packet_sent(t);     // :506
-  if (data_sent) timers_data_sent(t, now, timers_jitter_ms(seed, row));  // :508-510
-}
+struct TimersSent {  // send.go:498-510 for job j of a send-assign batch
+  KeptJobRows src;
+  const int32_t* sizes;
+  int64_t now;
+  uint32_t seed;
+  wgcs_timers* timers;
+  WGCS_HD void operator()(uint32_t j) const {
+    const uint32_t row = src.row(j);  // a dropped job: nothing was sent
+    if (row == WGCS_PEER_NONE) return;
+    bool data_sent = false;  // :498-502: a keepalive's slot has size 0
+    const int32_t* const sz = sizes + (uint64_t)j * src.jobs.max_segs;
+    for (int32_t k = 0; k < src.jobs.count[j]; ++k) data_sent |= sz[k] != 0;
+    wgcs_timers* const t = timers + row;
+    timers_traversal(t, now);  // :505
+    timers_packet_sent(t);     // :506
+    if (data_sent) timers_data_sent(t, now, timers_jitter_ms(seed, row));  // :508-510
+  }
+};
 
-// receive.go:486-494 for row c of the write builder's groups
-WGCS_HD void timers_received(uint32_t c, const wgcs_write_group* groups, int64_t now, const uint32_t* peer_rows,
-                             uint32_t n_ids, wgcs_timers* timers, uint32_t n_peers) {
-  if (groups[c].tail < 0) return;  // :486; an unused row, and dataPacketReceived implies a valid tail
-  const uint32_t row = rekey_peer_row(groups[c].peer, peer_rows, n_ids, n_peers);
-  if (row == WGCS_PEER_NONE) return;
-  wgcs_timers* const t = timers + row;
-  timers_traversal(t, now);   // :489
-  timers_packet_received(t);  // :490
-  if (groups[c].flags & WGCS_GROUP_DATA) timers_data_received(t, now);  // :492-494
-}
+struct TimersReceived {  // receive.go:486-494 for row c of the write builder's groups
+  GroupRows src;
+  int64_t now;
+  wgcs_timers* timers;
+  WGCS_HD void operator()(uint32_t c) const {
+    const uint32_t row = src.row(c);  // :486
+    if (row == WGCS_PEER_NONE) return;
+    wgcs_timers* const t = timers + row;
+    timers_traversal(t, now);   // :489
+    timers_packet_received(t);  // :490
+    if (src.flags(c) & WGCS_GROUP_DATA) timers_data_received(t, now);  // :492-494
+  }
+};
 
-// send.go:85-87 for peer row r of the start call
-WGCS_HD void timers_initiated_fresh(uint32_t r, const uint32_t* reasons, wgcs_timers* timers) {
-  if (reasons[r] & ~WGCS_REKEY_WANT_RETRY) timers[r].attempts = 0;
-}
+struct TimersFresh {  // send.go:85-87 for peer row r of the start call
+  const uint32_t* reasons;
+  wgcs_timers* timers;
+  WGCS_HD void operator()(uint32_t r) const {
+    if (reasons[r] & ~WGCS_REKEY_WANT_RETRY) timers[r].attempts = 0;
+  }
+};
 
-// send.go:117-126 for ticket k of the start call, once initiate has built its message
-WGCS_HD void timers_initiated(uint32_t k, const uint32_t* start_peer, const int32_t* init_status, int64_t now,
-                              uint32_t seed, wgcs_timers* timers, uint32_t n_peers) {
-  const uint32_t row = start_peer[k];
-  if (row >= n_peers || init_status[k] != WGCS_HS_INITIATED) return;
-  wgcs_timers* const t = timers + row;
-  timers_traversal(t, now);                                          // :117
-  timers_packet_sent(t);                                             // :118
-  timers_handshake_initiated(t, now, timers_jitter_ms(seed, row));   // :126
-}
+struct TimersInitiated {  // send.go:117-126 for ticket k of the start call, once initiate has built its message
+  TicketRows src;
+  int64_t now;
+  uint32_t seed;
+  wgcs_timers* timers;
+  WGCS_HD void operator()(uint32_t k) const {
+    const uint32_t row = src.row(k);
+    if (row == WGCS_PEER_NONE) return;
+    wgcs_timers* const t = timers + row;
+    timers_traversal(t, now);                                          // :117
+    timers_packet_sent(t);                                             // :118
+    timers_handshake_initiated(t, now, timers_jitter_ms(seed, row));   // :126
+  }
+};
 
-// receive.go:311-312 and send.go:158-160 for descriptor j of a respond batch
-WGCS_HD void timers_responded(uint32_t j, const wgcs_hs_resp* resp, const int32_t* gate, int64_t now,
-                              wgcs_timers* timers, uint32_t n_peers) {
-  if (gate[j] != WGCS_HS_RESPONDED) return;
-  const uint32_t row = resp[j].peer_row;
-  if (row >= n_peers) return;
-  wgcs_timers* const t = timers + row;
-  timers_traversal(t, now);        // receive.go:311
-  timers_packet_received(t);       // :312
-  timers_session_derived(t, now);  // send.go:158
-  timers_traversal(t, now);        // :159
-  timers_packet_sent(t);           // :160
-}
+struct TimersResponded {  // receive.go:311-312 and send.go:158-160 for descriptor j of a respond batch
+  RespondedRows src;
+  int64_t now;
+  wgcs_timers* timers;
+  WGCS_HD void operator()(uint32_t j) const {
+    const uint32_t row = src.row(j);
+    if (row == WGCS_PEER_NONE) return;
+    wgcs_timers* const t = timers + row;
+    timers_traversal(t, now);        // receive.go:311
+    timers_packet_received(t);       // :312
+    timers_session_derived(t, now);  // send.go:158
+    timers_traversal(t, now);        // :159
+    timers_packet_sent(t);           // :160
+  }
+};
 
-// receive.go:339-348 for row q of a begin-initiator batch
-WGCS_HD void timers_finished(uint32_t q, const uint8_t* arena, const wgcs_aead_pkt* pkts, const int32_t* gate,
-                             const int32_t* begun, int64_t now, const wgcs_session_slot* hs_slots,
-                             uint32_t n_hs_slots, const wgcs_hs_state* states, uint32_t n_states, wgcs_timers* timers,
-                             wgcs_rekey* rekey, uint32_t n_peers) {
-  if (begun[q] != WGCS_HS_BEGUN) return;  // :342-345: goto skip
-  uint32_t f[4];
-  if (keypairs_initiator_fields(arena, pkts, gate, q, hs_slots, n_hs_slots, states, n_states, f) != kKeypairsTaken)
-    return;
-  const uint32_t row = f[0];
-  if (row >= n_peers) return;
-  wgcs_timers* const t = timers + row;
-  timers_traversal(t, now);                          // :339
-  timers_packet_received(t);                         // :340
-  timers_session_derived(t, now);                    // :346
-  timers_handshake_complete(t, rekey + row, now);    // :347
-  timers_or(&t->flags, WGCS_TIMERS_KEEPALIVE_NOW);   // :348
-}
+struct TimersFinished {  // receive.go:339-348 for row q of a begin-initiator batch
+  FinishedRows src;
+  const int32_t* begun;
+  int64_t now;
+  wgcs_timers* timers;
+  wgcs_rekey* rekey;
+  WGCS_HD void operator()(uint32_t q) const {
+    if (begun[q] != WGCS_HS_BEGUN) return;  // :342-345: goto skip
+    const uint32_t row = src.row(q);
+    if (row == WGCS_PEER_NONE) return;
+    wgcs_timers* const t = timers + row;
+    timers_traversal(t, now);                          // :339
+    timers_packet_received(t);                         // :340
+    timers_session_derived(t, now);                    // :346
+    timers_handshake_complete(t, rekey + row, now);    // :347
+    timers_or(&t->flags, WGCS_TIMERS_KEEPALIVE_NOW);   // :348
+  }
+};
 
-// receive.go:422-427 for row i of a keypairs-received batch
-WGCS_HD void timers_rotated(uint32_t i, const wgcs_aead_pkt* pkts, const uint32_t* rotated, int64_t now,
-                            const uint32_t* key_peer, uint32_t n_keys, const uint32_t* peer_rows, uint32_t n_ids,
-                            wgcs_timers* timers, wgcs_rekey* rekey, uint32_t n_peers) {
-  if (rotated[i] != 1) return;
-  const uint32_t key = pkts[i].key;
-  if (key >= n_keys) return;
-  const uint32_t row = rekey_peer_row(key_peer[key], peer_rows, n_ids, n_peers);
-  if (row == WGCS_PEER_NONE) return;
-  timers_handshake_complete(timers + row, rekey + row, now);  // :426
-}
+struct TimersRotated {  // receive.go:422-427 for row i of a keypairs-received batch
+  KeyRows src;
+  const uint32_t* rotated;
+  int64_t now;
+  wgcs_timers* timers;
+  wgcs_rekey* rekey;
+  WGCS_HD void operator()(uint32_t i) const {
+    if (rotated[i] != 1) return;
+    const uint32_t row = src.row(i);
+    if (row == WGCS_PEER_NONE) return;
+    timers_handshake_complete(timers + row, rekey + row, now);  // :426
+  }
+};
 
 // ---- expiry, timers.go:73-144, over the peer rows in three passes ----
 

@@ -198,7 +198,7 @@ def main() -> None:
             rounds = [(events(recv), events(copy)) for _ in range(3)]
             print(json.dumps({**base, "metric": "endpoint_recv_us", "unit": "us", "rows": n, "value": med(rounds, 0),
                               "recv_us": [r[0] for r in rounds], "plain_copy_us_same_rows": [r[1] for r in rounds],
-                              "kernel": "endpoint_recv_kernel", "timing": timing}), flush=True)
+                              "kernel": "each_kernel<EndpointRecv>", "timing": timing}), flush=True)
         return
 
     for n in (65536, 1024):
@@ -227,7 +227,7 @@ def main() -> None:
                 torch.cuda.synchronize()
                 assert d_tab.cpu().numpy().tobytes() == tab.tobytes() and not bool(d_claim.any())
                 names = ("endpoint_set_received_us", "timers_received_us_same_groups",
-                         "endpoint_set_claim_kernel + endpoint_set_commit_kernel")
+                         "each_kernel<EndpointSetClaim<GroupRows>> + each_kernel<EndpointSetCommit<GroupRows>>")
             else:
                 tm["flags"][::2] |= ep.TIMERS_CLEAR_SRC
                 peer = (np.arange(n) % distinct).astype(np.uint32)
@@ -258,7 +258,8 @@ def main() -> None:
                 torch.cuda.synchronize()
                 assert d_dst.cpu().numpy().tobytes() == want[0].tobytes() and d_tab.cpu().numpy().tobytes() == tab.tobytes()
                 assert d_tx.cpu().numpy().view(np.uint64).tolist() == want[3].tolist()
-                names = ("endpoint_dst_jobs_us", "timers_sent_us_same_jobs", "endpoint_dst_read_kernel + endpoint_dst_clear_kernel")
+                names = ("endpoint_dst_jobs_us", "timers_sent_us_same_jobs",
+                         "each_kernel<EndpointDstJobs> + each_kernel<EndpointDstClear<KeptJobRows>>")
             if args.mode == "dst":
                 rounds = [(events(ours), events(beside), events(rearm)) for _ in range(3)]
                 more = {"includes_rearm_us": [r[2] for r in rounds],
